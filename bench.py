@@ -8,17 +8,27 @@ A step = one pass of the hot path over one batch resident in HBM:
 normalize x2 -> mix_up -> normalize -> STFT/|X|^2/mel -> PCEN -> WRN forward
 -> loss -> backward -> gradient all-reduce (N > 1) -> Adam.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
       N > 1: the driver starts it under torch.distributed.run (RANK/WORLD_SIZE
       set); started directly with --gpus N it launches the N ranks itself.
       ACFE_DIST_BACKEND=gloo rehearses the multi-rank path on one GPU (RCCL
       needs one GPU per rank).
 
-Prints ONE JSON line on rank 0.  `roofline` is measured live with HIP events
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K
+steps and prints the line.  `roofline` is measured live with HIP events
 around the dominant kernel (the forward of the stage-1 block-0 3x3 128->128
-convolution, 57 % of the model FLOPs) on the stream it runs on; the rocprofv3
-summaries under profiles/ are the cross-check.  `cpu_baseline` times the CPU
-restatement of the same step (oracle/, torch-CPU + numpy) on a bounded sample.
+convolution, 57 % of the model FLOPs) on the stream it runs on, inside the
+timed steps; the rocprofv3 summaries under profiles/ are the cross-check.
+
+--full adds what takes runs of its own: `cpu_baseline` times the CPU
+restatement of the same step (oracle/, torch-CPU + numpy) on a bounded sample
+(--no-cpu-baseline skips it), and the secondary workloads (wr_resnet
+training, configs I and S) run at reduced step counts (--no-extra skips them).
+
+--dump-outputs DIR writes what the last timed step returned to its caller
+(and the parameters it left behind) as DIR/<name>.npy in float32; the inputs
+and seeds depend on the arguments alone, so two builds can be compared
+output for output.
 """
 from __future__ import annotations
 
@@ -196,9 +206,14 @@ def main():
     ap.add_argument("--classes", type=int, default=50)
     ap.add_argument("--model", choices=["bird", "wrn"], default="bird")
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU baseline and the secondary workloads (a plain run times the headline "
+                         "workload only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extra", dest="extra", action="store_false",
-                    help="skip the secondary workloads (wr_resnet training, configs I and S) of the default run")
+                    help="with --full: skip the secondary workloads (wr_resnet training, configs I and S)")
     ap.add_argument("--cpu-batch", type=int, default=8)
     ap.add_argument("--cpu-steps", type=int, default=10)
     ap.add_argument("--clips", type=int, default=4096, help="e2e: clips written to the TFRecord set")
@@ -208,10 +223,17 @@ def main():
                     help="train = T1/T8 (the driver's line); infer = config I (B=256 fp32 wr_resnet fwd); "
                          "stream = config S (60-min recording, 3 s / 1.5 s windows, batch 1024)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.workload == "e2e":
+        if a.dump_outputs:
+            ap.error("--dump-outputs: the e2e workload's batches depend on the reader threads' timing")
         return run_e2e(a)
     if a.workload != "train":
-        print(json.dumps(run_inference(a)), flush=True)
+        line, last = run_inference(a)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, last)
+        print(json.dumps(line), flush=True)
         return 0
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -239,8 +261,11 @@ def main():
 
     ops.set_seed_rank(rank)  # per-replica dropout masks
     dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float32
-    out, _ = train_line(a.model, dtype, a.classes, a.batch, a.steps, a.warmup, rank, world, dev, dist)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    out, trainer, last = train_line(a.model, dtype, a.classes, a.batch, a.steps, a.warmup, rank, world, dev, dist)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {**last, "params": trainer.arena.flat})
+    del trainer, last
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.cpu_batch, a.cpu_steps, a.model, a.classes)
         # the other workloads' CPU rows (tools/cpu_baseline.py on a GPU box's
         # host cores, same host type), newest round first
@@ -252,17 +277,17 @@ def main():
                                                 **json.loads(suite.read_text())["rows"]}
             except (ValueError, KeyError):
                 pass
-    if rank == 0 and world == 1 and a.extra and a.model == "bird" and a.dtype == "bf16" and a.batch == 512:
+    if (rank == 0 and world == 1 and a.full and a.extra and a.model == "bird" and a.dtype == "bf16"
+            and a.batch == 512):
         # the secondary workloads of BASELINE.json at reduced step counts, so
-        # the driver's own run observes them: the metric's named model
+        # a --full run observes them: the metric's named model
         # (wr_resnet training, T1 shape), config I and config S
         torch.cuda.empty_cache()
-        w, _ = train_line("wrn", torch.bfloat16, 2, 512, 5, 2, 0, 1, dev, dist)
-        out["wrn"] = _summary(w)
+        out["wrn"] = _summary(train_line("wrn", torch.bfloat16, 2, 512, 5, 2, 0, 1, dev, dist)[0])
         torch.cuda.empty_cache()
-        out["infer"] = _summary(run_inference(a, workload="infer", steps=5, warmup=2, emit=False))
+        out["infer"] = _summary(run_inference(a, workload="infer", steps=5, warmup=2)[0])
         torch.cuda.empty_cache()
-        out["stream"] = _summary(run_inference(a, workload="stream", steps=2, warmup=1, emit=False))
+        out["stream"] = _summary(run_inference(a, workload="stream", steps=2, warmup=1)[0])
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -280,6 +305,22 @@ def active_switches():
             "library": os.path.relpath(_lib.LIB_PATH, ROOT) if hasattr(_lib, "LIB_PATH") else None}
 
 
+DUMP_MAX_BYTES = 16 << 20  # per array; a run dumps at most three
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each device tensor of `arrays` as <path>/<name>.npy in
+    float32; of an array above DUMP_MAX_BYTES a fixed sample (seeded, sorted
+    flat indices) is kept."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        v = t.detach().float().cpu().numpy()
+        if v.nbytes > DUMP_MAX_BYTES:
+            idx = np.sort(np.random.default_rng(20260227).choice(v.size, DUMP_MAX_BYTES // 4, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(v, dtype=np.float32))
+
+
 def _summary(o):
     """The fields of a secondary workload's line kept in the main line."""
     keep = ("metric", "value", "unit", "ms_per_step", "ms_per_step_median", "steps", "warmup", "dtype", "config",
@@ -292,7 +333,8 @@ def _summary(o):
 
 def train_line(model_name, dtype, classes, batch, steps, warmup, rank, world, dev, dist):
     """Time `steps` training steps (after `warmup`) of model_name on HBM-resident
-    synthetic batches; returns (the bench line without cpu_baseline, trainer)."""
+    synthetic batches; returns (the bench line without cpu_baseline, trainer,
+    what the last timed step returned)."""
     from acfe import ops
     from acfe.train import FrontEnd, Trainer
 
@@ -335,7 +377,7 @@ def train_line(model_name, dtype, classes, batch, steps, warmup, rank, world, de
     t0 = time.perf_counter()
     sev[0].record()
     for i in range(steps):
-        loss, _ = step(i)
+        loss, logits = step(i)
         sev[i + 1].record()
     torch.cuda.synchronize()
     if world > 1:
@@ -427,7 +469,7 @@ def train_line(model_name, dtype, classes, batch, steps, warmup, rank, world, de
         "final_loss": round(loss_v, 5),
         "switches": active_switches(),
     }
-    return out, trainer
+    return out, trainer, {"loss": loss, "logits": logits}
 
 
 def launch_ranks(n: int) -> int:
@@ -558,11 +600,11 @@ def run_e2e(a):
     print(json.dumps(out), flush=True)
 
 
-def run_inference(a, workload=None, steps=None, warmup=None, emit=True):
+def run_inference(a, workload=None, steps=None, warmup=None):
     """Configs I and S of BASELINE.json (one GPU; shards over ranks with no
     collective, so only the single-GPU replica is measured here).  Returns the
-    line.  `workload` given (the default run's secondary lines): the config's
-    own settings, not the command line's.
+    line and what the last timed step returned.  `workload` given (the --full
+    run's secondary lines): the config's own settings, not the command line's.
 
     I: fused normalize/STFT/mel/PCEN + wr_resnet forward, batch 256, fp32.
     S: one 60-min 48 kHz recording resident in HBM, 3 s windows every 1.5 s
@@ -628,7 +670,7 @@ def run_inference(a, workload=None, steps=None, warmup=None, emit=True):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(steps):
-        step(i)
+        probs = step(i)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     ops.watch_conv(target.weight, None)
@@ -668,7 +710,7 @@ def run_inference(a, workload=None, steps=None, warmup=None, emit=True):
                          "GBps": round(avg_clips * FRONTEND_BYTES_PER_CLIP / (mel_ms * 1e-3) / 1e9, 2)},
         "switches": active_switches(),
     }
-    return out
+    return out, {"probs": torch.cat(probs) if stream else probs}
 
 
 if __name__ == "__main__":

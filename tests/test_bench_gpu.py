@@ -20,6 +20,40 @@ from conftest import ROOT
 pytestmark = pytest.mark.gpu
 
 
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run times the headline workload alone (the CPU baseline and the
+    secondary workloads belong to --full) and --dump-outputs writes what the
+    last timed step returned -- loss [1], logits [batch, classes] -- and the
+    parameter arena after it, as float32 .npy files."""
+    import numpy as np
+
+    if torch.cuda.device_count() < 1:
+        pytest.skip("no GPU")
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dump = tmp_path / "out"
+    cmd = [sys.executable, "-u", str(ROOT / "bench.py"), "--gpus", "1", "--batch", "8", "--classes", "10",
+           "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump)]
+    r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["n_gpus"] == 1
+    assert out["unit"] == "clips/s" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+    assert out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(8 / (out["ms_per_step"] * 1e-3), rel=2e-3)
+    assert not {"cpu_baseline", "wrn", "infer", "stream"} & set(out)
+    assert sorted(p.name for p in dump.iterdir()) == ["logits.npy", "loss.npy", "params.npy"]
+    got = {p.stem: np.load(p) for p in dump.iterdir()}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in got.values())
+    assert got["loss"].shape == (1,) and got["logits"].shape == (8, 10)
+    assert got["loss"][0] == pytest.approx(out["final_loss"], abs=1e-5)
+    assert got["params"].ndim == 1 and 0 < got["params"].nbytes <= 16 << 20
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+
+
 def test_bench_two_ranks_gloo():
     if torch.cuda.device_count() < 1:  # counting devices does not initialise HIP
         pytest.skip("no GPU")

@@ -18,7 +18,7 @@ step() { # name timeout cmd...
 }
 bp() { # name benchargs...  (bench line + rocprof of the same command)
   local name=$1; shift
-  step ${name}_bench 600 python bench.py "$@"
+  step ${name}_bench 600 python bench.py --full "$@"
   step ${name}_prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${name}_prof -o run -- \
       python bench.py --no-cpu-baseline "$@"
 }

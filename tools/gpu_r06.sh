@@ -18,7 +18,7 @@ step() { # name timeout cmd...
 }
 bp() { # name benchargs...  (bench line + rocprof of the same command)
   local name=$1; shift
-  step ${name}_bench 600 python bench.py "$@"
+  step ${name}_bench 600 python bench.py --full "$@"
   step ${name}_prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${name}_prof -o run -- \
       python bench.py --no-cpu-baseline --no-extra "$@"
 }
@@ -29,7 +29,7 @@ for w in "$@"; do
     testsall) timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 120 --timeout-method thread > $O/testsall.log 2>&1
               rc=$?; echo "== testsall rc=$rc"; grep -E "FAILED|ERROR|passed|failed" $O/testsall.log | tail -30
               case $rc in 0|1) ;; *) exit $rc ;; esac ;;
-    bdef) step bdef 600 python bench.py ;;
+    bdef) step bdef 600 python bench.py --full ;;
     r64t) step r64t 300 python -u -m pytest tests/test_r64_gpu.py -x -v --timeout 120 --timeout-method thread ;;
     t1x) step t1x_bench 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra ;;
     wrnq) step wrnq_bench 300 python bench.py --model wrn --classes 2 --steps 8 --warmup 3 --no-cpu-baseline --no-extra ;;
