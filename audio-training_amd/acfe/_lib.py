@@ -59,6 +59,7 @@ SIGNATURES: dict[str, list] = {
     "acfe_conv_r64_enable": [I32],
     "acfe_mel_w5_frames": [I32],
     "acfe_conv2d_wgrad_bnbwd_rows": [I32] * 5,
+    "acfe_conv2d_wgrad_halo_info": [I32, I32, I32, I32, I32, I32, I32, P],
     "acfe_conv2d_wgrad_bnbwd": [P, I32, I32, I32, I32, P, P, I32, P, P, I32, P, P, F32, C.c_uint64, P, P, F32, P, P,
                                 P],
     "acfe_conv2d_dropout_keep_supported": [I32] * 6,
@@ -170,6 +171,19 @@ def check(rc: int, what: str = "") -> int:
 
 def call(name: str, *args) -> int:
     return check(getattr(lib, name)(*args), name)
+
+
+HALO_FIELDS = ("cw", "nr", "wp", "nchunk", "sp", "edge", "qs", "qse")
+
+
+def wgrad_halo_info(N, H, W, C, K, fold=False, unpool=False):
+    """acfe_conv2d_wgrad_halo_info as a dict of HALO_FIELDS (the launch plan of
+    the halo weight gradient, host only), or None when the halo kernel does not
+    take the shape."""
+    out = (I32 * 8)()
+    if not lib.acfe_conv2d_wgrad_halo_info(N, H, W, C, K, int(fold), int(unpool), out):
+        return None
+    return dict(zip(HALO_FIELDS, out))
 
 
 def exported_symbols() -> list[str]:

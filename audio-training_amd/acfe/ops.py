@@ -183,8 +183,11 @@ def keep_bits_ok(x, w, stride, pt, pl, P, Q, drop, want_stats) -> bool:
     N, H, W, C = x.shape
     K, R, S, _ = w.shape
     src = _pending(x)[0] if _pending(x) is not None else x  # (the BN input the prologue reads)
+    # (the only reader of the bits is the BN-fold weight gradient: shapes it
+    # does not take, an odd H among them, write none)
     return ((R, S, stride, pt, pl, P, Q) == (3, 3, 1, 1, 1, H, W) and src.is_contiguous()
-            and src.data_ptr() % 16 == 0 and bool(lib.acfe_conv2d_dropout_keep_supported(N, H, W, C, K, 1)))
+            and src.data_ptr() % 16 == 0 and bool(lib.acfe_conv2d_dropout_keep_supported(N, H, W, C, K, 1))
+            and lib.acfe_conv2d_wgrad_bnbwd_rows(N, H, W, C, K) > 0)
 
 
 def _conv_fwd(x, w, b, stride, pt, pl, P, Q, want_stats, drop=None, keep=None):

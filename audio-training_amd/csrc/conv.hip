@@ -4709,6 +4709,29 @@ ACFE_API int acfe_conv2d_wgrad_bnbwd_rows(int N, int H, int W, int C, int K) {
   return ok ? hp.nchunk * hp.sp : 0;
 }
 
+// The launch plan of the 3x3 stride-1 "same" bf16 weight gradient of the shape
+// (host only, no GPU call): out = {cw, nr, wp, nchunk, sp, edge, qs, qse} of
+// the halo_plan that wgrad_halo_launch runs for acfe_conv2d_wgrad (fold = unpool
+// = 0), acfe_conv2d_wgrad_bnbwd[_keep] (fold) or acfe_conv2d_wgrad_unpool
+// (unpool); 1 when k_wgrad3x3_halo takes the shape, else 0 and out zeroed.
+ACFE_API int acfe_conv2d_wgrad_halo_info(int N, int H, int W, int C, int K, int fold, int unpool, int* out) {
+  if (!out) return 0;
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || (fold && unpool)) return 0;
+  long long splits, chunk;
+  wgrad_plan((long long)N * H * W, 9 * C, K, &splits, &chunk);
+  if (!halo_ok(N, C, K, 3, 3, 1, H, W, splits)) return 0;
+  if (fold && acfe_conv2d_wgrad_bnbwd_rows(N, H, W, C, K) <= 0) return 0;
+  if (unpool && !acfe_conv2d_pool_supported(N, H, W, C, K, 3, 3, ACFE_DTYPE_BF16)) return 0;
+  ConvGeom g = make_geom(N, H, W, C, K, 3, 3, 1, 1, 1, H, W, 64, 128);
+  static const float fold_tag = 0.f;
+  if (fold) g.fb_sc = &fold_tag;  // (halo_plan only tests it: the fold's launches)
+  const HaloPlan hp = halo_plan(g, unpool != 0, splits);
+  const int v[8] = {hp.cw, hp.nr, hp.wp, hp.nchunk, hp.sp, hp.edge ? 1 : 0, hp.qs, hp.qse};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
+  return 1;
+}
+
 static int wgrad_bnbwd_impl(const void* x, int N, int H, int W, int C, const void* gy, const void* u_bn, int K,
                             const float* scale, const float* shift, int relu, const float* coef, const void* add,
                             float drop_rate, unsigned long long seed, const uint8_t* keep, void* dy, float* dw,
@@ -5097,10 +5120,16 @@ ACFE_API int acfe_conv2d_fwd_bn(const void* x, int N, int H, int W, int C, const
 // gradient reads them instead of regenerating the pair hashes
 ACFE_API int acfe_conv2d_dropout_keep_supported(int N, int H, int W, int C, int K, int dtype) {
   const int nch = C / 64;
-  return acfe::r64_enabled() && dtype == ACFE_DTYPE_BF16 && N > 0 && H > 0 && W > 0 && K == 64 && C % 64 == 0 &&
-         (nch == 1 || nch == 2 || nch == 4) && (long long)H * W * C * 2 < (1ll << 31) &&
-         (long long)H * W * K * 2 < (1ll << 31) && (long long)N * H * W * K < (1ll << 32) &&
-         (long long)N * ((H + 7) / 8) * ((W + 63) / 64) < (1ll << 31);
+  if (!(acfe::r64_enabled() && dtype == ACFE_DTYPE_BF16 && N > 0 && H > 0 && W > 0 && K == 64 && C % 64 == 0 &&
+        (nch == 1 || nch == 2 || nch == 4) && (long long)H * W * C * 2 < (1ll << 31) &&
+        (long long)H * W * K * 2 < (1ll << 31) && (long long)N * H * W * K < (1ll << 32) &&
+        (long long)N * ((H + 7) / 8) * ((W + 63) / 64) < (1ll << 31)))
+    return 0;
+  // the grids keep_launch's launch_r64 would take (the statistics slab always
+  // there): a slab too small for the remainder-column launch is not covered
+  const ConvGeom g = make_geom(N, H, W, C, K, 3, 3, 1, 1, 1, H, W, 64, K);
+  acfe::R64Grid rg;
+  return acfe::r64_grid(g, true, grid_m_for(g.M, 1), &rg) ? 1 : 0;
 }
 
 static int keep_launch(ConvGeom& g, const void* x, const void* wpacked, const float* bias, void* y,

@@ -195,6 +195,13 @@ int launch_plain1w(const ConvGeom& g, const void* x, const void* wp, const float
 int launch_r64(const ConvGeom& g, const void* x, const void* wp, const float* bias, void* y, double* stats,
                int srows, hipStream_t s, const char* what, int pm);
 bool r64_enabled();
+// launch_r64's tile counts and grids (main launch, remainder-column launch)
+struct R64Grid {
+  int rem, tiles_h, tiles_w, tiles_he, tiles_we;
+  long long nt, nte;
+  int gp, gpe;
+};
+bool r64_grid(const ConvGeom& g, bool stats, int srows, R64Grid* o);
 // acfe_conv2d_dgrad_bn at K = C = 128 on the same kernel (PM 5: dX + the BN backward reduce sums)
 int launch_dgradbn1w(const ConvGeom& g, const void* dy, const void* wflip, void* dx, double* part, int srows,
                      hipStream_t s, const char* what);

@@ -599,6 +599,44 @@ static bool r64_on() {
 
 bool r64_enabled() { return r64_on(); }
 
+// The grids of launch_r64's launches (host only; acfe_conv2d_dropout_keep_supported
+// asks it too, so that it says no exactly where the launch would):
+// the image's whole 64-pixel columns in 8 x 64 tiles, the Q % 64 pixels
+// left of each row (when Q >= 64) in 32 x 16 tiles by a second launch that
+// writes the statistics slab rows after the first one's (the per-pixel
+// values are the same either way: each accumulator's MFMA sequence does not
+// depend on the tiling).  false: the slab has no row left for the second
+// launch (or a tile count past 2^31) -- not this kernel's case.
+bool r64_grid(const ConvGeom& g, bool stats, int srows, R64Grid* o) {
+  const int rem = g.Q >= 64 ? g.Q % 64 : 0;
+  const int tiles_h = (g.P + 7) / 8, tiles_w = rem ? g.Q / 64 : (g.Q + 63) / 64;
+  const long long nt = (long long)g.N * tiles_h * tiles_w;
+  const int tiles_he = (g.P + 31) / 32, tiles_we = (rem + 15) / 16;
+  const long long nte = rem ? (long long)g.N * tiles_he * tiles_we : 0;
+  if (nt >= (1ll << 31) || nte >= (1ll << 31)) return false;
+  auto grid_for = [&](long long n, int rows_left) {
+    int gp = 256;
+    if (gp > n) gp = (int)n;
+    if (gp >= 64) gp &= ~7;
+    if (stats && gp > rows_left) gp = rows_left;  // one statistics slab row per workgroup
+    return gp;
+  };
+  // (small slabs: leave the second launch up to half of the rows)
+  const int gp = grid_for(nt, nte && stats ? srows - (int)(srows / 2 < nte ? srows / 2 : nte) : srows);
+  const int gpe = nte ? grid_for(nte, srows - gp) : 0;
+  if (nte && gpe <= 0) return false;
+  o->rem = rem;
+  o->tiles_h = tiles_h;
+  o->tiles_w = tiles_w;
+  o->tiles_he = tiles_he;
+  o->tiles_we = tiles_we;
+  o->nt = nt;
+  o->nte = nte;
+  o->gp = gp;
+  o->gpe = gpe;
+  return true;
+}
+
 int launch_r64(const ConvGeom& g, const void* x, const void* wp, const float* bias, void* y, double* stats,
                int srows, hipStream_t s, const char* what, int pm) {
   // 3x3 stride 1 "same"-shaped halo (pads 0..2), K = 64, C in {64, 128, 256},
@@ -619,28 +657,11 @@ int launch_r64(const ConvGeom& g, const void* x, const void* wp, const float* bi
   if (pm != 0 && pm != 3 && pm != 4 && pm != 5) return ACFE_E_INVAL;
   if (pm == 4 && !stats) return ACFE_E_INVAL;
   const bool st = stats != nullptr;
-  // the image's whole 64-pixel columns in 8 x 64 tiles, the Q % 64 pixels
-  // left of each row (when Q >= 64) in 32 x 16 tiles by a second launch that
-  // writes the statistics slab rows after the first one's (the per-pixel
-  // values are the same either way: each accumulator's MFMA sequence does not
-  // depend on the tiling)
-  const int rem = g.Q >= 64 ? g.Q % 64 : 0;
-  const int tiles_h = (g.P + 7) / 8, tiles_w = rem ? g.Q / 64 : (g.Q + 63) / 64;
-  const long long nt = (long long)g.N * tiles_h * tiles_w;
-  const int tiles_he = (g.P + 31) / 32, tiles_we = (rem + 15) / 16;
-  const long long nte = rem ? (long long)g.N * tiles_he * tiles_we : 0;
-  if (nt >= (1ll << 31) || nte >= (1ll << 31)) return ACFE_E_INVAL;
-  auto grid_for = [&](long long n, int rows_left) {
-    int gp = 256;
-    if (gp > n) gp = (int)n;
-    if (gp >= 64) gp &= ~7;
-    if (stats && gp > rows_left) gp = rows_left;  // one statistics slab row per workgroup
-    return gp;
-  };
-  // (small slabs: leave the second launch up to half of the rows)
-  const int gp = grid_for(nt, nte && stats ? srows - (int)(srows / 2 < nte ? srows / 2 : nte) : srows);
-  const int gpe = nte ? grid_for(nte, srows - gp) : 0;
-  if (nte && gpe <= 0) return ACFE_E_INVAL;
+  R64Grid rg;
+  if (!r64_grid(g, st, srows, &rg)) return ACFE_E_INVAL;
+  const int rem = rg.rem, tiles_h = rg.tiles_h, tiles_w = rg.tiles_w, tiles_he = rg.tiles_he, tiles_we = rg.tiles_we;
+  const long long nt = rg.nt, nte = rg.nte;
+  const int gp = rg.gp, gpe = rg.gpe;
 #define R64L(SW_, PM_, NCH_, PRO_, ST_, G_, TH_, TW_, NT_, WO_, SR_)                                              \
   hipLaunchKernelGGL((k_conv3x3_r64<PM_, NCH_, PRO_, ST_, SW_>), dim3(G_), dim3(512), 0, s, g, (const uint16_t*)x, \
                      (const uint16_t*)wp, bias, (uint16_t*)y, stats, TH_, TW_, (int)(NT_), srows, WO_, SR_)

@@ -271,6 +271,16 @@ int acfe_conv2d_wgrad(const void* x, int N, int H, int W, int C, const void* dy,
  * acfe_conv2d_wgrad.  _rows: 0 when the shape is not covered (then
  * acfe_bn_bwd_apply_ex + acfe_conv2d_wgrad). */
 int acfe_conv2d_wgrad_bnbwd_rows(int N, int H, int W, int C, int K);
+/* Which halo weight-gradient launch a bf16 3x3 stride-1 "same" shape takes
+ * (host only, no GPU call; the launcher's own plan functions): out[8] = {cw
+ * (channels per chunk), nr (output rows per step), wp (pixel groups of waves),
+ * nchunk, sp (splits per chunk), edge (1: the W % 64 last pixels of each row
+ * run as a second launch of 16-pixel segments), qs (64-pixel segment columns
+ * of the first launch), qse (16-pixel columns of the second)} for the plain
+ * weight gradient (fold = unpool = 0), the BN-backward fold (fold = 1) or the
+ * pooled-gradient form (unpool = 1).  Returns 1 when the halo kernel takes the
+ * shape (fold: where _wgrad_bnbwd_rows > 0), else 0 with out zeroed. */
+int acfe_conv2d_wgrad_halo_info(int N, int H, int W, int C, int K, int fold, int unpool, int* out);
 int acfe_conv2d_wgrad_bnbwd(const void* x, int N, int H, int W, int C, const void* gy, const void* u_bn, int K,
                             const float* scale, const float* shift, int relu, const float* coef, const void* add,
                             float drop_rate, unsigned long long seed, void* dy, float* dw, float beta,

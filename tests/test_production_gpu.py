@@ -580,15 +580,18 @@ def test_model_stem_bn_fusion(env, cuda):
             assert torch.equal(g1[n], g0[n]), n
 
 
-@pytest.mark.parametrize("C,K,H,W", [(128, 32, 32, 64), (32, 128, 32, 64), (32, 256, 16, 32), (16, 256, 16, 32),
-                                     (64, 64, 64, 128), (128, 64, 64, 128), (64, 64, 14, 100), (256, 256, 22, 86),
-                                     (256, 16, 16, 32), (128, 16, 16, 40), (16, 64, 64, 100), (16, 64, 15, 70),
-                                     (64, 16, 20, 70), (128, 128, 22, 100), (64, 64, 10, 150)],
+# (the last field: the 16-pixel remainder columns the plan must show, 0 = no remainder launch)
+@pytest.mark.parametrize("C,K,H,W,qse", [(128, 32, 32, 64, 0), (32, 128, 32, 64, 0), (32, 256, 16, 32, 0),
+                                         (16, 256, 16, 32, 0), (64, 64, 64, 128, 0), (128, 64, 64, 128, 0),
+                                         (64, 64, 14, 100, 0), (256, 256, 22, 86, 2), (256, 16, 16, 32, 0),
+                                         (128, 16, 16, 40, 0), (16, 64, 64, 100, 3), (16, 64, 15, 70, 0),
+                                         (64, 16, 20, 70, 0), (128, 128, 22, 100, 3), (64, 64, 10, 150, 0),
+                                         (64, 64, 16, 150, 2)],
                          ids=["s2-21", "s2-2b", "s3-2b-b6", "s3-2b", "k64-rowpair", "k64-rowpair-2chunks",
                               "k64-rowpair-partial", "wrn-s3-256", "s3-21-k16", "k16-1chunk-partial",
                               "wrn-s1-2a-c16", "c16-k64-oddrows", "k16-c64-chunks", "k128-rem-oddrows",
-                              "k64-rem-2cols"])
-def test_wgrad_halo_narrow(env, cuda, C, K, H, W):
+                              "k64-masked-cols-10rows", "k64-rem-2cols-16rows"])
+def test_wgrad_halo_narrow(env, cuda, C, K, H, W, qse):
     """k_wgrad3x3_halo for the stage-2/3 layers whose channel count is the
     feature height: K = 32 (branch21 128 -> 32) and the 16 / 32-channel
     chunks (branch2b 32 -> 128 / 256, 16 -> 256), and the K = 64 layers'
@@ -600,10 +603,18 @@ def test_wgrad_halo_narrow(env, cuda, C, K, H, W):
     wr_resnet's stage-1 16 -> 64 (two pixel groups of waves writing separate
     split slabs; two rows per step, one for an odd row count), at 32 clips and
     the production split count, against float64.  Widths past a multiple of
-    64 run their last Q % 64 pixels as 16-pixel segments (r06; a partial last
-    row group at 22 / 10 rows, two remainder columns at W = 150)."""
+    64 run their last Q % 64 pixels as 16-pixel segments where the plan says
+    edge (acfe_conv2d_wgrad_halo_info): K = 128 at 22 x 100 and K = 256 at 22
+    x 86 (a partial last row group, three / two remainder columns), K = 64 at
+    16 x 150 (two remainder columns, the last one 6 pixels) and the C = 16 ->
+    K = 64 layer at 64 x 100.  K = 64 takes them for whole 8-row groups
+    only (P % 8 == 0): 14 x 100 and 10 x 150 run masked 64-pixel columns."""
     ops, call, lib, ptr, stream = env
+    from acfe._lib import wgrad_halo_info
     N = 32
+    plan = wgrad_halo_info(N, H, W, C, K)
+    assert plan is not None
+    assert (plan["edge"], plan["qse"]) == (int(qse > 0), qse), plan
     x, w, b, g = _data(N, H, W, C, K, 307, cuda)
     dy = (torch.randn((N, H, W, K), generator=g) * 0.5).to(BF).to(cuda)
     ws = torch.empty((lib.acfe_conv2d_wgrad_workspace(N, H, W, C, K, 3, 3, H, W),), device=cuda)

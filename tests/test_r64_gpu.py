@@ -188,16 +188,29 @@ def test_r64_dgrad(env, cuda, N, H, W, Kd, relu):
     assert ((s - ref).abs() <= 1e-5 * ref.abs().clamp_min(1.0) + 1e-2).all()
 
 
-@pytest.mark.parametrize("C,pro", [(64, False), (64, True), (128, True)], ids=["c64", "c64-bn", "c128-bn"])
-def test_keep_bits(env, cuda, C, pro):
+_KEEP_CASES = [(64, False), (64, True), (128, True), (256, True)]
+_KEEP_IDS = ["c64", "c64-bn", "c128-bn", "c256-bn"]
+
+
+@pytest.mark.parametrize("C,pro,N,H,W", [(c, p, 6, 14, 100) for c, p in _KEEP_CASES] +
+                         [(c, p, 2, 16, 100) for c, p in _KEEP_CASES],
+                         ids=_KEEP_IDS + [i + "-h16" for i in _KEEP_IDS])
+def test_keep_bits(env, cuda, C, pro, N, H, W):
     """The dropout keep bits (acfe_conv2d_fwd_dropout_keep / _bn_keep): the
     forward's outputs are bit-identical to the forward without them, the bits
     are acfe_dropout's mask of the same (rate, seed, element index), and the
     BN-fold weight gradient reading them (acfe_conv2d_wgrad_bnbwd_keep) is
-    bit-identical to the one regenerating the mask -- dY, dW and the slab."""
+    bit-identical to the one regenerating the mask -- dY, dW and the slab.
+    The fold wgrad takes row pairs (even H); W = 100 is a partial 64-pixel
+    column: at H = 14 the fold masks it (P % 8 != 0), at H = 16 it runs the
+    36 last pixels as three 16-pixel remainder columns (the KEEP remainder
+    kernel).  C = 256: four chunks."""
     ops, call, lib, ptr, stream = env
-    N, H, W, K = 6, 14, 100, 64  # (the fold wgrad takes row pairs: even H; a partial 64-column tile)
+    from acfe._lib import wgrad_halo_info
+    K = 64
     assert lib.acfe_conv2d_dropout_keep_supported(N, H, W, C, K, 1)
+    plan = wgrad_halo_info(N, H, W, C, K, fold=True)
+    assert (plan["nchunk"], plan["edge"], plan["qse"]) == (C // 64, int(H % 8 == 0), 3 if H % 8 == 0 else 0), plan
     g = torch.Generator(device="cpu").manual_seed(C + pro)
     x = torch.randn((N, H, W, C), generator=g).to(BF).to(cuda)
     w = (torch.randn((K, 3, 3, C), generator=g) * (1.0 / (3 * C ** 0.5))).to(cuda)
