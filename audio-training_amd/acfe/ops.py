@@ -1,4 +1,5 @@
-"""Autograd operators over the acfe model kernels (csrc/conv.hip, csrc/nn.hip).
+"""Autograd operators over the acfe model kernels (csrc/conv.hip with
+csrc/pool1w.hip and csrc/rows64.hip, csrc/stem.hip, csrc/c1bn.hip, csrc/nn.hip).
 
 Every forward/backward here is one or more calls through the C ABI; torch is
 used only for device memory (torch.empty), streams and autograd bookkeeping.

@@ -19,9 +19,8 @@
 //                 with both operands staged m-major and fed to the MFMA through
 //                 ds_read_b64_tr_b16 (bf16) -- per-split fp32 slabs, then a
 //                 deterministic reduction.
-//  * stem         C = 1 direct kernels (the 3 identical input channels of
-//                 tfdataset.py:2053 are folded into one by summing the stem
-//                 weights over Cin; exact up to fp reassociation).
+// The C = 1 stem is stem.hip; the one-wave K = C = 128 and the K = 64 row-halo
+// kernels are pool1w.hip and rows64.hip.
 #include "conv_common.h"
 
 // Timing-only ablations of the BN-fold weight gradient (they skip work and
@@ -55,10 +54,6 @@ __device__ __forceinline__ void mma(f4& acc, const uint4& a, const uint4& b, flo
   acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
 }
-__device__ __forceinline__ uint16_t cvt_out(float v, uint16_t) { return f2bf(v); }
-__device__ __forceinline__ float cvt_out(float v, float) { return v; }
-__device__ __forceinline__ float to_f(uint16_t v) { return bf2f(v); }
-__device__ __forceinline__ float to_f(float v) { return v; }
 
 template <typename T, int BM, int BN>
 constexpr int conv_smem() {
@@ -3838,7 +3833,73 @@ static ConvGeom make_geom(int N, int H, int W, int C, int K, int R, int S, int s
 
 static int pick_bn(int K) { return K <= 32 ? 32 : (K <= 64 ? 64 : 128); }
 
+// the BatchNormalization (+ReLU) prologue / the residual epilogue of the geometry
+static void set_prologue(ConvGeom& g, const float* sc, const float* sh, int relu, void* out) {
+  g.pro_sc = sc;
+  g.pro_sh = sh;
+  g.pro_relu = relu ? 1 : 0;
+  g.pro_out = (uint16_t*)out;
+}
+static void set_residual(ConvGeom& g, const void* res, int relu) {
+  g.res = (const uint16_t*)res;
+  g.res_relu = relu ? 1 : 0;
+}
 
+// k_conv_fwd_p preconditions: whole K-tiles per tap, whole N tiles, a
+// 64-bit tap mask, 32-bit pixel index and < 2 GiB of input per M tile
+static bool fwd_p_ok(const ConvGeom& g, int BN) {
+  const long long img = (long long)g.H * g.W * g.C * 2;
+  const long long span = ((256 + (long long)g.P * g.Q - 1) / ((long long)g.P * g.Q) + 1) * img;
+  return g.C % 64 == 0 && g.K % BN == 0 && g.R * g.S <= 64 && g.R < 32 && g.M < (1ll << 31) && span < (1ll << 31);
+}
+
+// k_conv_fwd_p (RES: with the residual epilogue of acfe_conv2d_fwd_add), persistent:
+// one 512-thread workgroup per CU (256 CUs), a multiple of 8
+template <int BN, bool RES>
+static int launch_fwd_p(const ConvGeom& g, const void* x, const void* wp, const float* bias, void* y, double* stats,
+                        int srows, hipStream_t s, const char* what) {
+  const int ny = g.Kp / BN, tiles = (int)((g.M + 255) / 256);
+  int gp = 256 / ny;
+  if (gp > tiles) gp = tiles;
+  if (gp >= 64) gp &= ~7;
+  hipLaunchKernelGGL((k_conv_fwd_p<BN, false, RES>), dim3(gp, ny), dim3(512), 0, s, g, (const uint16_t*)x,
+                     (const uint16_t*)wp, bias, (uint16_t*)y, stats, tiles, srows);
+  return launch_rc(what);
+}
+
+// k_conv3x3_cw's case: 3x3 stride-1 "same", 32 -> 128 / 16 -> 256 channels
+// (wr_resnet_bird's stage-2 / 3 branch2b), 32-bit element indices, 16-B rows
+static bool cw_ok(const ConvGeom& g, const void* x, const void* wp, const void* y) {
+  return g.R == 3 && g.S == 3 && g.st == 1 && g.pt == 1 && g.pl == 1 && g.P == g.H && g.Q == g.W &&
+         ((g.C == 32 && g.K == 128) || (g.C == 16 && g.K == 256 && g.Kdp >= 160)) && g.Kp == g.K && g.ldy == g.K &&
+         g.M * g.K < (1ll << 32) && ((uintptr_t)x & 15) == 0 && ((uintptr_t)wp & 15) == 0 && ((uintptr_t)y & 15) == 0;
+}
+
+typedef void (*CwKernel)(ConvGeom, const uint16_t*, const uint16_t*, const float*, uint16_t*, double*, int, int, int,
+                         int);
+template <int CW, int KB, bool RES>
+static CwKernel cw_kernel(int segw, bool drop) {
+  if constexpr (!RES) {
+    if (drop) return segw == 64 ? k_conv3x3_cw<CW, KB, 64, true> : k_conv3x3_cw<CW, KB, 32, true>;
+  }
+  return segw == 64 ? k_conv3x3_cw<CW, KB, 64, false, RES> : k_conv3x3_cw<CW, KB, 32, false, RES>;
+}
+
+// k_conv3x3_cw (RES: with the residual epilogue, no dropout) on 256- / 128-pixel
+// tiles, 64 (32 for narrow images) wide; ACFE_E_INVAL when not its case
+template <bool RES>
+static int launch_cw(const ConvGeom& g, const void* x, const void* wp, const float* bias, void* y, double* stats,
+                     int srows, hipStream_t s, const char* what) {
+  if (!cw_ok(g, x, wp, y) || (RES && g.drop.on)) return ACFE_E_INVAL;
+  const int segw = g.Q <= 32 ? 32 : 64, tr = (g.K == 256 ? 128 : 256) / segw;
+  const int tiles_h = (g.P + tr - 1) / tr, tiles_w = (g.Q + segw - 1) / segw;
+  const long long nt = (long long)g.N * tiles_h * tiles_w;
+  if (nt >= (1ll << 31)) return ACFE_E_INVAL;
+  const CwKernel k = g.C == 32 ? cw_kernel<32, 128, RES>(segw, g.drop.on) : cw_kernel<16, 256, RES>(segw, g.drop.on);
+  hipLaunchKernelGGL(k, dim3(tile_grid(nt, stats != nullptr, srows)), dim3(512), 0, s, g, (const uint16_t*)x,
+                     (const uint16_t*)wp, bias, (uint16_t*)y, stats, tiles_h, tiles_w, (int)nt, srows);
+  return launch_rc(what);
+}
 
 // k_conv3x3_narrow with 8 waves per workgroup (4 waves measured slower, r02v)
 template <int KB, int SW>
@@ -3868,13 +3929,7 @@ static int launch_fwd_t(const ConvGeom& g, const void* x, const void* wp, const 
       const int tiles_h = (g.P + tr - 1) / tr, tiles_w = (g.Q + 63) / 64;  // partial last column tile
       const long long nt = (long long)g.N * tiles_h * tiles_w;
       if (nt < (1ll << 31)) {
-        int gp = 256;
-        if (gp > nt) gp = (int)nt;
-        if (gp >= 64) gp &= ~7;
-        // each workgroup writes statistics slab row blockIdx.x: never more
-        // workgroups than the caller's slab rows (narrow images have more
-        // tiles than 128-pixel slab rows)
-        if (stats && gp > grid_m) gp = grid_m;
+        const int gp = tile_grid(nt, stats != nullptr, grid_m);
         if constexpr (BN == 128) {
           // one wave per SIMD (pool1w.hip), the previous tile's epilogue beside this tile's MFMAs
           const int rc = launch_plain1w(g, x, wp, bias, y, stats, grid_m, s, "acfe_conv2d_fwd", 0);
@@ -3893,21 +3948,7 @@ static int launch_fwd_t(const ConvGeom& g, const void* x, const void* wp, const 
         return launch_rc("acfe_conv2d_fwd");
       }
     }
-    // k_conv_fwd_p preconditions: whole K-tiles per tap, whole N tiles, a
-    // 64-bit tap mask, 32-bit pixel index and < 2 GiB of input per M tile
-    const long long img = (long long)g.H * g.W * g.C * 2;
-    const long long span = ((256 + (long long)g.P * g.Q - 1) / ((long long)g.P * g.Q) + 1) * img;
-    if (g.C % 64 == 0 && g.K % BN == 0 && g.R * g.S <= 64 && g.R < 32 && g.M < (1ll << 31) &&
-        span < (1ll << 31)) {
-      // persistent: one 512-thread workgroup per CU (256 CUs), a multiple of 8
-      const int ny = g.Kp / BN, tiles = (int)((g.M + 255) / 256);
-      int gp = 256 / ny;
-      if (gp > tiles) gp = tiles;
-      if (gp >= 64) gp &= ~7;
-      hipLaunchKernelGGL((k_conv_fwd_p<BN>), dim3(gp, ny), dim3(512), 0, s, g, (const uint16_t*)x,
-                         (const uint16_t*)wp, bias, (uint16_t*)y, stats, tiles, grid_m);
-      return launch_rc("acfe_conv2d_fwd");
-    }
+    if (fwd_p_ok(g, BN)) return launch_fwd_p<BN, false>(g, x, wp, bias, y, stats, grid_m, s, "acfe_conv2d_fwd");
   }
   if (g.C % TT<T>::GR == 0)
     hipLaunchKernelGGL((k_conv_fwd_g<T, 128, BN, WM, WN>), grid, dim3(256), 0, s, g, (const T*)x,
@@ -3950,10 +3991,7 @@ general:
       const int tiles_h = (g.P + 7) / 8, tiles_w = (g.Q + 63) / 64;
       const long long nt = (long long)g.N * tiles_h * tiles_w;
       if (nt < (1ll << 31)) {
-        int gp = 256;
-        if (gp > nt) gp = (int)nt;
-        if (gp >= 64) gp &= ~7;
-        if (stats && gp > grid_m) gp = grid_m;  // one statistics slab row per workgroup
+        const int gp = tile_grid(nt, stats != nullptr, grid_m);
         if (g.drop.on)
           hipLaunchKernelGGL(k_conv3x3_c16<true>, dim3(gp), dim3(512), 0, s, g, (const uint16_t*)x,
                              (const uint16_t*)wp, bias, (uint16_t*)y, stats, tiles_h, tiles_w, (int)nt, grid_m);
@@ -3963,32 +4001,9 @@ general:
         return launch_rc("acfe_conv2d_fwd(c16)");
       }
     }
-    if (g.R == 3 && g.S == 3 && g.st == 1 && g.pt == 1 && g.pl == 1 && g.P == g.H && g.Q == g.W &&
-        ((g.C == 32 && g.K == 128) || (g.C == 16 && g.K == 256 && g.Kdp >= 160)) && g.Kp == g.K && g.ldy == g.K &&
-        g.M * g.K < (1ll << 32) && ((uintptr_t)x & 15) == 0 && ((uintptr_t)wp & 15) == 0 && ((uintptr_t)y & 15) == 0) {
-      // 32 -> 128 / 16 -> 256 (k_conv3x3_cw): 256- / 128-pixel tiles, 64 (32 for narrow images) wide
-      const int segw = g.Q <= 32 ? 32 : 64, tr = (g.K == 256 ? 128 : 256) / segw;
-      const int tiles_h = (g.P + tr - 1) / tr, tiles_w = (g.Q + segw - 1) / segw;
-      const long long nt = (long long)g.N * tiles_h * tiles_w;
-      if (nt < (1ll << 31)) {
-        int gp = 256;
-        if (gp > nt) gp = (int)nt;
-        if (gp >= 64) gp &= ~7;
-        if (stats && gp > grid_m) gp = grid_m;  // one statistics slab row per workgroup
-#define CWL(CW_, KB_, SW_, D_)                                                                              \
-  hipLaunchKernelGGL((k_conv3x3_cw<CW_, KB_, SW_, D_>), dim3(gp), dim3(512), 0, s, g, (const uint16_t*)x,    \
-                     (const uint16_t*)wp, bias, (uint16_t*)y, stats, tiles_h, tiles_w, (int)nt, grid_m)
-#define CWD(CW_, KB_)                                                                                       \
-  if (segw == 64) {                                                                                         \
-    if (g.drop.on) CWL(CW_, KB_, 64, true); else CWL(CW_, KB_, 64, false);                                  \
-  } else {                                                                                                  \
-    if (g.drop.on) CWL(CW_, KB_, 32, true); else CWL(CW_, KB_, 32, false);                                  \
-  }
-        if (g.C == 32) { CWD(32, 128) } else { CWD(16, 256) }
-#undef CWD
-#undef CWL
-        return launch_rc("acfe_conv2d_fwd(cw)");
-      }
+    {
+      const int rc = launch_cw<false>(g, x, wp, bias, y, stats, grid_m, s, "acfe_conv2d_fwd(cw)");
+      if (rc != ACFE_E_INVAL) return rc;
     }
     if (g.R == 3 && g.S == 3 && g.st == 1 && g.pt == 1 && g.pl == 1 && g.P == g.H && g.Q == g.W &&
         g.C % 64 == 0 && (g.K == 32 || g.K == 16) && g.C * g.K <= 4096 && g.ldy == g.K &&
@@ -3999,10 +4014,7 @@ general:
       const int tiles_h = (g.P + tr - 1) / tr, tiles_w = (g.Q + segw - 1) / segw;
       const long long nt = (long long)g.N * tiles_h * tiles_w;
       if (nt < (1ll << 31)) {
-        int gp = 256;
-        if (gp > nt) gp = (int)nt;
-        if (gp >= 64) gp &= ~7;
-        if (stats && gp > grid_m) gp = grid_m;  // one statistics slab row per workgroup
+        const int gp = tile_grid(nt, stats != nullptr, grid_m);
         if (g.K == 32) {
           if (segw == 64) launch_narrow<32, 64>(g, x, wp, bias, y, stats, tiles_h, tiles_w, nt, grid_m, gp, s);
           else launch_narrow<32, 32>(g, x, wp, bias, y, stats, tiles_h, tiles_w, nt, grid_m, gp, s);
@@ -4402,7 +4414,10 @@ static void wgrad_combine(const float* ws, int nsplit, long long n, float beta, 
   }
 }
 
-static void wgrad_plan(long long M, int kd, int K, long long* splits_o, long long* chunk_o) {
+struct WgradPlan {
+  long long splits, chunk;
+};
+static WgradPlan wgrad_plan(long long M, int kd, int K) {
   const int bmw = K <= 32 ? 32 : (K <= 64 ? 64 : 128);
   const long long tiles = (long long)((kd + 127) / 128) * ((K + bmw - 1) / bmw);
   // target workgroup count of the split-K grid: 4096 measured 1.1 ms/step
@@ -4416,14 +4431,21 @@ static void wgrad_plan(long long M, int kd, int K, long long* splits_o, long lon
   splits = (M + chunk - 1) / chunk;
   if (splits < 1) splits = 1;
   splits = (splits + 7) / 8 * 8;
-  *splits_o = splits;
-  *chunk_o = chunk;
+  return {splits, chunk};
 }
 
 ACFE_API long long acfe_conv2d_wgrad_workspace(int N, int H, int W, int C, int K, int R, int S, int P, int Q) {
-  long long splits, chunk;
-  wgrad_plan((long long)N * P * Q, R * S * C, K, &splits, &chunk);
-  return splits * K * (long long)(R * S * C);  // floats
+  return wgrad_plan((long long)N * P * Q, R * S * C, K).splits * K * (long long)(R * S * C);  // floats
+}
+
+// the split slabs [used][K][kd] of a weight-gradient launch -> dW = beta * dW + their sum
+static int wgrad_finish(const float* ws, int used, int K, int kd, float beta, float* dw, hipStream_t s,
+                        const char* what) {
+  const long long n = (long long)K * kd;
+  int grid = cdiv((n + 3) / 4, 256);
+  if (grid > 2048) grid = 2048;
+  wgrad_combine(ws, used, n, beta, dw, grid, s);
+  return launch_rc(what);
 }
 
 template <typename T, int BMW>
@@ -4443,20 +4465,70 @@ static int launch_wgrad_t(const ConvGeom& g, const void* x, const void* dy, floa
   return launch_rc("acfe_conv2d_wgrad");
 }
 
-// k_wgrad3x3_halo launch (3x3 stride 1; C % 64 == 0 with K in {32, 64, 128,
-// 256}, or C in {16, 32} with K in {128, 256}; a partial last 64-pixel column
-// segment is masked): split count within the planned workspace (`splits`),
-// returned in *used.
+// ---- k_wgrad3x3_halo dispatch: one table of its instantiations; halo_plan
+// looks the shape's row up, and the launcher and the host-only queries
+// (acfe_conv2d_wgrad_halo_info, acfe_conv2d_wgrad_bnbwd_rows) decide from it
+typedef void (*HaloKernel)(ConvGeom, const uint16_t*, const uint16_t*, float*, int, int, int, const uint8_t*, int, int,
+                           int);
+// One row per k_wgrad3x3_halo instantiation: its SEGW = 64 kernel and, where
+// the Q % 64 remainder columns have their own launch, the SEGW = 16 one.
+struct HaloRow {
+  int kb, cw, nr;
+  bool unp, bwd, keep;
+  HaloKernel main, edge;
+};
+template <int KB, int CW, int NR, bool UNP = false, bool BWD = false, bool KEEP = false>
+static constexpr HaloRow halo_row() {
+  return {KB, CW, NR, UNP, BWD, KEEP, k_wgrad3x3_halo<KB, UNP, CW, NR, BWD, KEEP>, nullptr};
+}
+template <int KB, int CW, int NR, bool BWD = false, bool KEEP = false>
+static constexpr HaloRow halo_row_edge() {
+  return {KB, CW, NR, false, BWD, KEEP, k_wgrad3x3_halo<KB, false, CW, NR, BWD, KEEP>,
+          k_wgrad3x3_halo<KB, false, CW, NR, BWD, KEEP, 16>};
+}
+static const HaloRow halo_rows[] = {
+    // plain dY
+    halo_row<16, 128, 1>(),   // wr_resnet_bird stage 3 (256 -> 16)
+    halo_row<16, 64, 1>(),    // K = 16 on 64-channel chunks
+    halo_row<32, 64, 1>(),    // (18 MFMAs per wave per segment)
+    halo_row<32, 64, 2>(),    // the stage-2 branch21 (128 -> 32): 36 MFMAs per wave per two-row step
+    halo_row<64, 16, 1>(),    // C = 16 -> K = 64 (wr_resnet's stage-1 conv2a)
+    halo_row_edge<64, 16, 2>(),
+    halo_row<64, 64, 1>(),
+    halo_row_edge<64, 64, 2>(),
+    halo_row<128, 32, 1>(),   // the stage-2 branch2b (32 -> 128)
+    halo_row_edge<128, 64, 1>(),
+    halo_row<256, 16, 1>(),   // stage 3 (16 -> 256)
+    halo_row_edge<256, 32, 1>(),  // stage 3 (32 -> 256); wr_resnet's stage 3 (256 -> 256)
+    // dY unpooled from the 2x2 max-pool's gradient (acfe_conv2d_wgrad_unpool)
+    halo_row<64, 64, 1, true>(),
+    halo_row<64, 64, 2, true>(),
+    halo_row<128, 64, 1, true>(),  // (two rows per step spill: 138 VGPRs)
+    // dY formed from the BN backward while staging (acfe_conv2d_wgrad_bnbwd);
+    // (K = 128, one row per step: 19 VGPRs spilled -- not covered)
+    halo_row<32, 64, 2, false, true>(),
+    halo_row_edge<64, 16, 2, true>(),
+    halo_row_edge<64, 64, 2, true>(),
+    halo_row_edge<64, 64, 2, true, true>(),  // the forward's dropout keep bits (k_conv3x3_r64 PM 4)
+};
+static const HaloRow* halo_find(int kb, int cw, int nr, bool unp, bool bwd, bool keep) {
+  for (const HaloRow& r : halo_rows)
+    if (r.kb == kb && r.cw == cw && r.nr == nr && r.unp == unp && r.bwd == bwd && r.keep == keep) return &r;
+  return nullptr;
+}
+
 struct HaloPlan {
+  const HaloRow* row;  // null: k_wgrad3x3_halo has no such case
   int cw, nr, wp, nchunk, nseg, sp, per;
-  bool c16k64, k16c64;
-  // the Q % 64 remainder columns as 16-pixel segments (4 nr rows each) by a
-  // second launch over the same grid (plain K = 64 / 128 and the K = 64 BN
-  // fold): qs whole 64-pixel segment columns, then qse 16-pixel ones from wofs
+  // the Q % 64 remainder columns as 16-pixel segments (4 nr rows each) by the
+  // row's second kernel over the same grid: qs whole 64-pixel segment columns,
+  // then qse 16-pixel ones from wofs
   bool edge;
   int qs, qse, wofs, nsege, pere;
 };
-static HaloPlan halo_plan(const ConvGeom& g, bool amax, long long splits) {
+// unpool: dY from the pooled gradient + argmax bytes; fold: the BN backward
+// formed while staging; keep: the fold with the forward's dropout keep bits
+static HaloPlan halo_plan(const ConvGeom& g, bool unpool, bool fold, bool keep, long long splits) {
   HaloPlan hp;
   // 16 / 32-channel layers: one chunk of C; K = 256 (wr_resnet's stage-3
   // 256 -> 256): 32-channel chunks, so the K x 9 x CW accumulators stay 36
@@ -4477,17 +4549,14 @@ static HaloPlan halo_plan(const ConvGeom& g, bool amax, long long splits) {
   // block) pairs x two pixel groups (one 32-pixel half each), 72 KB of LDS ->
   // 2 workgroups per CU
   const bool k16c64 = cw == 64 && g.K == 16;
-  const int nr = ((cw == 64 || c16k64) && g.P % 2 == 0 && (g.K == 64 || (g.K == 32 && !amax))) ? 2 : 1;
+  const int nr = ((cw == 64 || c16k64) && g.P % 2 == 0 && (g.K == 64 || (g.K == 32 && !unpool))) ? 2 : 1;
   const int wp = (c16k64 || k16c64) ? 2 : 1;
   const int rem = g.Q >= 64 ? g.Q % 64 : 0;
+  const HaloRow* row = halo_find(g.K, cw, nr, unpool, fold, keep);
   // (the BN fold writes its dY rows: whole 4 nr row groups only, and the
-  // plain K = 64 kernel splits exactly as the fold does, so that their dW
-  // stay bit-identical; K = 128 / 256 mask the rows of a partial last group)
-  // (C = 16 -> K = 64, two pixel groups of waves: the same rule as K = 64)
-  const bool edge = rem && !amax &&
-                    ((((cw == 64 && wp == 1) || c16k64) && g.K == 64 && nr == 2 && g.P % 8 == 0) ||
-                     (!g.fb_sc && wp == 1 &&
-                      ((cw == 64 && g.K == 128 && nr == 1) || (cw == 32 && g.K == 256 && nr == 1))));
+  // plain two-row kernels split exactly as the fold does, so that their dW
+  // stay bit-identical; the one-row kernels mask the rows of a partial last group)
+  const bool edge = row && row->edge && rem && (nr == 1 || g.P % 8 == 0);
   const int qs = edge ? g.Q / 64 : (g.Q + 63) / 64;
   const int nchunk = g.C / cw, nseg = (int)((long long)g.N * (g.P / nr) * qs);
   // c16k64: 75 KB of LDS and 114 VGPRs -> two workgroups per CU
@@ -4496,6 +4565,7 @@ static HaloPlan halo_plan(const ConvGeom& g, bool amax, long long splits) {
   sp &= ~7;
   if (sp < 8) sp = 8;
   if (sp > splits) sp = (int)splits;  // splits is a multiple of 8 (wgrad_plan)
+  hp.row = row;
   hp.cw = cw;
   hp.nr = nr;
   hp.wp = wp;
@@ -4503,8 +4573,6 @@ static HaloPlan halo_plan(const ConvGeom& g, bool amax, long long splits) {
   hp.nseg = nseg;
   hp.sp = sp;
   hp.per = (nseg + sp - 1) / sp;
-  hp.c16k64 = c16k64;
-  hp.k16c64 = k16c64;
   hp.edge = edge;
   hp.qs = qs;
   hp.qse = edge ? (rem + 15) / 16 : 0;
@@ -4514,98 +4582,23 @@ static HaloPlan halo_plan(const ConvGeom& g, bool amax, long long splits) {
   return hp;
 }
 
+// k_wgrad3x3_halo launch (3x3 stride 1; C % 64 == 0 with K in {16, 32, 64, 128,
+// 256}, or C in {16, 32} with K in {128, 256}, or C = 16 with K = 64; a partial
+// last 64-pixel column segment is masked): split count within the planned
+// workspace (`splits`), returned in *used.  ACFE_E_INVAL: no table row.
 static int wgrad_halo_launch(const ConvGeom& g, const void* x, const void* dy, const uint8_t* amax, float* ws,
                              long long splits, hipStream_t s, int* used) {
-  const HaloPlan hp = halo_plan(g, amax != nullptr, splits);
-  const int cw = hp.cw, nr = hp.nr, wp = hp.wp, nchunk = hp.nchunk, nseg = hp.nseg, sp = hp.sp, per = hp.per;
-  const bool c16k64 = hp.c16k64, k16c64 = hp.k16c64;
-  const dim3 gr(nchunk * sp);
-  const int qs = hp.qs, qse = hp.qse, wofs = hp.wofs, nsege = hp.nsege, pere = hp.pere;
-  if (g.fb_sc) {  // acfe_conv2d_wgrad_bnbwd: the BN backward formed while staging dY
-#define WB(KB_, CW_, NR_, KP_)                                                                                  \
-  hipLaunchKernelGGL((k_wgrad3x3_halo<KB_, false, CW_, NR_, true, KP_>), gr, dim3(512), 0, s, g,                 \
-                     (const uint16_t*)x, (const uint16_t*)dy, ws, nchunk, nseg, per, nullptr, qs, 0, 0)
-#define WBE(KB_, CW_, NR_, KP_)                                                                                 \
-  hipLaunchKernelGGL((k_wgrad3x3_halo<KB_, false, CW_, NR_, true, KP_, 16>), gr, dim3(512), 0, s, g,             \
-                     (const uint16_t*)x, (const uint16_t*)dy, ws, nchunk, nsege, pere, nullptr, qse, wofs, 1)
-    if (amax || (wp != 1 && !c16k64)) return ACFE_E_INVAL;
-    // keep bits: the stage-1 K = 64 fold only (the forward that writes them: k_conv3x3_r64 PM 4)
-    if (g.keep_in && !(cw == 64 && g.K == 64 && nr == 2 && !c16k64 && g.drop.on)) return ACFE_E_INVAL;
-    if (c16k64 && nr == 2) {
-      WB(64, 16, 2, false);
-      if (hp.edge) WBE(64, 16, 2, false);
-    } else if (cw == 64 && g.K == 64 && nr == 2 && g.keep_in) {
-      WB(64, 64, 2, true);
-      if (hp.edge) WBE(64, 64, 2, true);
-    } else if (cw == 64 && g.K == 64 && nr == 2) {
-      WB(64, 64, 2, false);
-      if (hp.edge) WBE(64, 64, 2, false);
-    } else if (cw == 64 && g.K == 32 && nr == 2) WB(32, 64, 2, false);
-    else return ACFE_E_INVAL;
-#undef WBE
-#undef WB
-    *used = sp * wp;
-    return launch_rc("acfe_conv2d_wgrad_bnbwd");
-  }
-#define WH(KB_, U_)                                                                                              \
-  hipLaunchKernelGGL((k_wgrad3x3_halo<KB_, U_>), gr, dim3(512), 0, s, g, (const uint16_t*)x, (const uint16_t*)dy, \
-                     ws, nchunk, nseg, per, amax, qs, 0, 0)
-#define WHC(KB_, CW_)                                                                                              \
-  hipLaunchKernelGGL((k_wgrad3x3_halo<KB_, false, CW_>), gr, dim3(512), 0, s, g, (const uint16_t*)x,               \
-                     (const uint16_t*)dy, ws, nchunk, nseg, per, nullptr)
-  if (cw == 128) {  // wr_resnet_bird stage 3 (256 -> 16)
-    WHC(16, 128);
-  } else if (k16c64) {
-    WHC(16, 64);
-  } else if (c16k64) {
-    if (nr == 2) {
-      hipLaunchKernelGGL((k_wgrad3x3_halo<64, false, 16, 2>), gr, dim3(512), 0, s, g, (const uint16_t*)x,
-                         (const uint16_t*)dy, ws, nchunk, nseg, per, nullptr, qs, 0, 0);
-      if (hp.edge)
-        hipLaunchKernelGGL((k_wgrad3x3_halo<64, false, 16, 2, false, false, 16>), gr, dim3(512), 0, s, g,
-                           (const uint16_t*)x, (const uint16_t*)dy, ws, nchunk, nsege, pere, nullptr, qse, wofs, 1);
-    } else WHC(64, 16);
-  } else if (cw == 32) {  // the stage-2/3 branch2b (32 -> 128 / 256); wr_resnet's stage 3 (256 -> 256)
-    if (g.K == 128) WHC(128, 32);
-    else {
-      hipLaunchKernelGGL((k_wgrad3x3_halo<256, false, 32>), gr, dim3(512), 0, s, g, (const uint16_t*)x,
-                         (const uint16_t*)dy, ws, nchunk, nseg, per, nullptr, qs, 0, 0);
-      if (hp.edge)
-        hipLaunchKernelGGL((k_wgrad3x3_halo<256, false, 32, 1, false, false, 16>), gr, dim3(512), 0, s, g,
-                           (const uint16_t*)x, (const uint16_t*)dy, ws, nchunk, nsege, pere, nullptr, qse, wofs, 1);
-    }
-  } else if (cw == 16) {  // stage 3 (16 -> 256)
-    WHC(256, 16);
-  } else if (g.K == 128) {
-    if (amax) WH(128, true);
-    else {
-      WH(128, false);
-      if (hp.edge)
-        hipLaunchKernelGGL((k_wgrad3x3_halo<128, false, 64, 1, false, false, 16>), gr, dim3(512), 0, s, g,
-                           (const uint16_t*)x, (const uint16_t*)dy, ws, nchunk, nsege, pere, nullptr, qse, wofs, 1);
-    }
-  } else if (g.K == 64) {
-    if (amax && nr == 2)
-      hipLaunchKernelGGL((k_wgrad3x3_halo<64, true, 64, 2>), gr, dim3(512), 0, s, g, (const uint16_t*)x,
-                         (const uint16_t*)dy, ws, nchunk, nseg, per, amax, qs, 0, 0);
-    else if (amax) WH(64, true);
-    else if (nr == 2) {
-      hipLaunchKernelGGL((k_wgrad3x3_halo<64, false, 64, 2>), gr, dim3(512), 0, s, g, (const uint16_t*)x,
-                         (const uint16_t*)dy, ws, nchunk, nseg, per, nullptr, qs, 0, 0);
-      if (hp.edge)
-        hipLaunchKernelGGL((k_wgrad3x3_halo<64, false, 64, 2, false, false, 16>), gr, dim3(512), 0, s, g,
-                           (const uint16_t*)x, (const uint16_t*)dy, ws, nchunk, nsege, pere, nullptr, qse, wofs, 1);
-    } else WH(64, false);
-  } else if (nr == 2) {  // the stage-2 branch21 (128 -> 32): 36 MFMAs per wave per two-row step
-    hipLaunchKernelGGL((k_wgrad3x3_halo<32, false, 64, 2>), gr, dim3(512), 0, s, g, (const uint16_t*)x,
-                       (const uint16_t*)dy, ws, nchunk, nseg, per, nullptr);
-  } else {
-    WH(32, false);  // (18 MFMAs per wave per segment)
-  }
-#undef WHC
-#undef WH
-  *used = sp * wp;
-  return launch_rc(amax ? "acfe_conv2d_wgrad_unpool" : "acfe_conv2d_wgrad(halo)");
+  const bool fold = g.fb_sc != nullptr;  // acfe_conv2d_wgrad_bnbwd: the BN backward formed while staging dY
+  const HaloPlan hp = halo_plan(g, amax != nullptr, fold, g.keep_in != nullptr, splits);
+  if (!hp.row) return ACFE_E_INVAL;
+  const dim3 gr(hp.nchunk * hp.sp);
+  const uint16_t *xx = (const uint16_t*)x, *dd = (const uint16_t*)dy;
+  hipLaunchKernelGGL(hp.row->main, gr, dim3(512), 0, s, g, xx, dd, ws, hp.nchunk, hp.nseg, hp.per, amax, hp.qs, 0, 0);
+  if (hp.edge)  // adds its partial slabs into the first launch's
+    hipLaunchKernelGGL(hp.row->edge, gr, dim3(512), 0, s, g, xx, dd, ws, hp.nchunk, hp.nsege, hp.pere, amax, hp.qse,
+                       hp.wofs, 1);
+  *used = hp.sp * hp.wp;
+  return launch_rc(fold ? "acfe_conv2d_wgrad_bnbwd" : amax ? "acfe_conv2d_wgrad_unpool" : "acfe_conv2d_wgrad(halo)");
 }
 
 // k_wgrad_row_halo launch (the (4, 10) head conv: bf16, stride 1, K = 128,
@@ -4646,10 +4639,8 @@ ACFE_API int acfe_conv2d_wgrad(const void* x, int N, int H, int W, int C, const 
   const int kd = R * S * C;
   if (N == 0) return hip_rc(hipMemsetAsync(dw, 0, sizeof(float) * K * kd, strm(stream)), "wgrad");
   const int bmw = K <= 32 ? 32 : (K <= 64 ? 64 : 128);
-  long long splits, chunk;
-  wgrad_plan(M, kd, K, &splits, &chunk);
+  auto [splits, chunk] = wgrad_plan(M, kd, K);
   ConvGeom g = make_geom(N, H, W, C, K, R, S, stride, pad_top, pad_left, P, Q, 64, 128);
-  g.ldy = K;
   int rc;
   if (dtype == ACFE_DTYPE_BF16 && halo_ok(N, C, K, R, S, stride, P, Q, splits)) {
     // halo-staged kernel; its split count stays within the planned workspace
@@ -4674,11 +4665,7 @@ ACFE_API int acfe_conv2d_wgrad(const void* x, int N, int H, int W, int C, const 
     else rc = launch_wgrad_t<float, 128>(g, x, dy, workspace, chunk, (int)splits, strm(stream));
     if (rc) return rc;
   }
-  const long long n = (long long)K * kd;
-  int grid = cdiv((n + 3) / 4, 256);
-  if (grid > 2048) grid = 2048;
-  wgrad_combine(workspace, (int)splits, n, beta, dw, grid, strm(stream));
-  return launch_rc("acfe_conv2d_wgrad(reduce)");
+  return wgrad_finish(workspace, (int)splits, K, kd, beta, dw, strm(stream), "acfe_conv2d_wgrad(reduce)");
 }
 
 // ------------------------------------------------------------------ wgrad + BN backward apply
@@ -4698,15 +4685,8 @@ ACFE_API int acfe_conv2d_wgrad(const void* x, int N, int H, int W, int C, const 
 // acfe_channel_sum_finalize) -- the separate apply pass over the tensor is not
 // run.  Same dW as acfe_conv2d_wgrad on that dy.
 ACFE_API int acfe_conv2d_wgrad_bnbwd_rows(int N, int H, int W, int C, int K) {
-  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0) return 0;
-  long long splits, chunk;
-  wgrad_plan((long long)N * H * W, 9 * C, K, &splits, &chunk);
-  if (!halo_ok(N, C, K, 3, 3, 1, H, W, splits)) return 0;
-  ConvGeom g = make_geom(N, H, W, C, K, 3, 3, 1, 1, 1, H, W, 64, 128);
-  const HaloPlan hp = halo_plan(g, false, splits);
-  // (K = 128, one row per step: 19 VGPRs spilled -- not covered)
-  const bool ok = (hp.c16k64 && hp.nr == 2) || (hp.cw == 64 && ((K == 64 || K == 32) && hp.nr == 2));
-  return ok ? hp.nchunk * hp.sp : 0;
+  int plan[8];
+  return acfe_conv2d_wgrad_halo_info(N, H, W, C, K, 1, 0, plan) ? plan[3] * plan[4] : 0;  // nchunk * sp
 }
 
 // The launch plan of the 3x3 stride-1 "same" bf16 weight gradient of the shape
@@ -4718,15 +4698,12 @@ ACFE_API int acfe_conv2d_wgrad_halo_info(int N, int H, int W, int C, int K, int 
   if (!out) return 0;
   for (int i = 0; i < 8; ++i) out[i] = 0;
   if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || (fold && unpool)) return 0;
-  long long splits, chunk;
-  wgrad_plan((long long)N * H * W, 9 * C, K, &splits, &chunk);
+  const long long splits = wgrad_plan((long long)N * H * W, 9 * C, K).splits;
   if (!halo_ok(N, C, K, 3, 3, 1, H, W, splits)) return 0;
-  if (fold && acfe_conv2d_wgrad_bnbwd_rows(N, H, W, C, K) <= 0) return 0;
   if (unpool && !acfe_conv2d_pool_supported(N, H, W, C, K, 3, 3, ACFE_DTYPE_BF16)) return 0;
-  ConvGeom g = make_geom(N, H, W, C, K, 3, 3, 1, 1, 1, H, W, 64, 128);
-  static const float fold_tag = 0.f;
-  if (fold) g.fb_sc = &fold_tag;  // (halo_plan only tests it: the fold's launches)
-  const HaloPlan hp = halo_plan(g, unpool != 0, splits);
+  const ConvGeom g = make_geom(N, H, W, C, K, 3, 3, 1, 1, 1, H, W, 64, 128);
+  const HaloPlan hp = halo_plan(g, unpool != 0, fold != 0, false, splits);
+  if (!hp.row) return 0;
   const int v[8] = {hp.cw, hp.nr, hp.wp, hp.nchunk, hp.sp, hp.edge ? 1 : 0, hp.qs, hp.qse};
   for (int i = 0; i < 8; ++i) out[i] = v[i];
   return 1;
@@ -4767,10 +4744,8 @@ static int wgrad_bnbwd_impl(const void* x, int N, int H, int W, int C, const voi
   if (((uintptr_t)gy | (uintptr_t)u_bn | (uintptr_t)dy | (uintptr_t)add) & 15) return ACFE_E_INVAL;
   const int rows = acfe_conv2d_wgrad_bnbwd_rows(N, H, W, C, K);
   if (!rows) return ACFE_E_INVAL;
-  long long splits, chunk;
-  wgrad_plan((long long)N * H * W, 9 * C, K, &splits, &chunk);
+  const long long splits = wgrad_plan((long long)N * H * W, 9 * C, K).splits;
   ConvGeom g = make_geom(N, H, W, C, K, 3, 3, 1, 1, 1, H, W, 64, 128);
-  g.ldy = K;
   g.drop = make_drop(drop_rate, seed);
   g.fb_x = (const uint16_t*)u_bn;
   g.fb_sc = scale;
@@ -4784,11 +4759,7 @@ static int wgrad_bnbwd_impl(const void* x, int N, int H, int W, int C, const voi
   int used = 0;
   int rc = wgrad_halo_launch(g, x, gy, nullptr, workspace, splits, strm(stream), &used);
   if (rc) return rc;
-  const long long n = (long long)K * 9 * C;
-  int grid = cdiv((n + 3) / 4, 256);
-  if (grid > 2048) grid = 2048;
-  wgrad_combine(workspace, used, n, beta, dw, grid, strm(stream));
-  return launch_rc("acfe_conv2d_wgrad_bnbwd(reduce)");
+  return wgrad_finish(workspace, used, K, 9 * C, beta, dw, strm(stream), "acfe_conv2d_wgrad_bnbwd(reduce)");
 }
 
 // ------------------------------------------------------------------ conv + 2x2 max-pool
@@ -4809,10 +4780,7 @@ static int launch_rows_tr(const ConvGeom& g, const void* x, const void* wp, cons
   if ((uintptr_t)y & 15) return ACFE_E_INVAL;  // 16-B epilogue stores
   const int tiles_h = (g.P + TR - 1) / TR, tiles_w = (g.Q + 63) / 64;
   const long long nt = (long long)g.N * tiles_h * tiles_w;
-  int gp = 256;
-  if (gp > nt) gp = (int)nt;
-  if (gp >= 64) gp &= ~7;
-  if (stats && gp > srows) gp = srows;  // one statistics slab row per workgroup
+  const int gp = tile_grid(nt, stats != nullptr, srows);
   hipLaunchKernelGGL((k_conv3x3_rows<KB, TR, PM, XR, PR>), dim3(gp), dim3(512), 0, s, g, (const uint16_t*)x,
                      (const uint16_t*)wp, bias, (uint16_t*)y, stats, tiles_h, tiles_w, (int)nt, srows, amax);
   return launch_rc(what);
@@ -4941,10 +4909,7 @@ ACFE_API int acfe_conv2d_fwd_pool_bn(const void* x, int N, int H, int W, int C, 
     return ACFE_E_INVAL;
   ConvGeom g = make_geom(N, H, W, C, K, 3, 3, 1, pad_top, pad_left, H, W, 64, K);
   g.drop = make_drop(drop_rate, seed);
-  g.pro_sc = bn_scale;
-  g.pro_sh = bn_shift;
-  g.pro_relu = bn_relu ? 1 : 0;
-  g.pro_out = (uint16_t*)x_bn_out;
+  set_prologue(g, bn_scale, bn_shift, bn_relu, x_bn_out);
   const int srows = grid_m_for(g.M, 1);
   return launch_rows<64, 1>(g, x, wpacked, bias, y, stats_partial, srows, argmax, strm(stream),
                             "acfe_conv2d_fwd_pool_bn");
@@ -4971,18 +4936,12 @@ ACFE_API int acfe_conv2d_wgrad_unpool(const void* x, int N, int H, int W, int C,
   if (!x || !dyp || !argmax || !dw || !workspace || !acfe_conv2d_pool_supported(N, H, W, C, K, 3, 3, dtype) ||
       ((uintptr_t)dyp & 15) || ((uintptr_t)argmax & 7))
     return ACFE_E_INVAL;
-  long long splits, chunk;
-  wgrad_plan((long long)N * H * W, 9 * C, K, &splits, &chunk);
-  ConvGeom g = make_geom(N, H, W, C, K, 3, 3, 1, pad_top, pad_left, H, W, 64, 128);
-  g.ldy = K;
+  const long long splits = wgrad_plan((long long)N * H * W, 9 * C, K).splits;
+  const ConvGeom g = make_geom(N, H, W, C, K, 3, 3, 1, pad_top, pad_left, H, W, 64, 128);
   int used = 0;
-  int rc = wgrad_halo_launch(g, x, dyp, argmax, workspace, splits, strm(stream), &used);
+  const int rc = wgrad_halo_launch(g, x, dyp, argmax, workspace, splits, strm(stream), &used);
   if (rc) return rc;
-  const long long n = (long long)K * 9 * C;
-  int grid = cdiv((n + 3) / 4, 256);
-  if (grid > 2048) grid = 2048;
-  wgrad_combine(workspace, used, n, beta, dw, grid, strm(stream));
-  return launch_rc("acfe_conv2d_wgrad_unpool(reduce)");
+  return wgrad_finish(workspace, used, K, 9 * C, beta, dw, strm(stream), "acfe_conv2d_wgrad_unpool(reduce)");
 }
 
 // Conv2D 3x3 "same" stride 1 whose output is summed with the block shortcut
@@ -5016,55 +4975,24 @@ ACFE_API int acfe_conv2d_fwd_add(const void* x, int N, int H, int W, int C, cons
     // generic kernel: 16-B residual / output rows
     if (((uintptr_t)y & 15) || ((uintptr_t)res & 15)) return ACFE_E_INVAL;
     ConvGeom g = make_geom(N, H, W, C, K, 3, 3, 1, pad_top, pad_left, H, W, 64, 128);
-    g.res = (const uint16_t*)res;
-    g.res_relu = relu ? 1 : 0;
+    set_residual(g, res, relu);
+    // the caller's slab rows, acfe_conv2d_stats_rows(N*H*W, K), are the generic
+    // kernel's grid rows -- what launch_fwd receives as grid_m (K % 128 == 0:
+    // ny output-channel tiles either way)
     const int ny = g.Kp / 128, gm = grid_m_for(g.M, ny);
     const int tiles_m = (int)((g.M + 127) / 128);
-    if (((C == 32 && K == 128) || (C == 16 && K == 256 && g.Kdp >= 160)) && pad_top == 1 && pad_left == 1 &&
-        g.M * K < (1ll << 32) && ((uintptr_t)x & 15) == 0 && ((uintptr_t)wpacked & 15) == 0) {
-      // k_conv3x3_cw with the residual epilogue (wr_resnet_bird's stage-2 / 3 branch2b)
-      const int segw = W <= 32 ? 32 : 64, tr = (K == 256 ? 128 : 256) / segw;
-      const int tiles_h = (H + tr - 1) / tr, tiles_w = (W + segw - 1) / segw;
-      const long long nt = (long long)N * tiles_h * tiles_w;
-      if (nt < (1ll << 31)) {
-        int gp = 256;
-        if (gp > nt) gp = (int)nt;
-        if (gp >= 64) gp &= ~7;
-        const int srows = acfe_conv2d_stats_rows(g.M, K);  // (the caller's slab rows)
-        if (stats_partial && gp > srows) gp = srows;
-#define CWA(CW_, KB_, SW_)                                                                                  \
-  hipLaunchKernelGGL((k_conv3x3_cw<CW_, KB_, SW_, false, true>), dim3(gp), dim3(512), 0, strm(stream), g,    \
-                     (const uint16_t*)x, (const uint16_t*)wpacked, bias, (uint16_t*)y, stats_partial, tiles_h, \
-                     tiles_w, (int)nt, srows)
-        if (C == 32) {
-          if (segw == 64) CWA(32, 128, 64); else CWA(32, 128, 32);
-        } else {
-          if (segw == 64) CWA(16, 256, 64); else CWA(16, 256, 32);
-        }
-#undef CWA
-        return launch_rc("acfe_conv2d_fwd_add(cw)");
-      }
-    }
-    const long long img = (long long)H * W * C * 2;
-    const long long span = ((256 + (long long)H * W - 1) / ((long long)H * W) + 1) * img;
-    if (C % 64 == 0 && span < (1ll << 31)) {
-      // the persistent GEMM with the residual epilogue (wr_resnet's stage 3)
-      const int tiles = (int)((g.M + 255) / 256);
-      int gp = 256 / ny;
-      if (gp > tiles) gp = tiles;
-      if (gp >= 64) gp &= ~7;
-      hipLaunchKernelGGL((k_conv_fwd_p<128, false, true>), dim3(gp, ny), dim3(512), 0, strm(stream), g,
-                         (const uint16_t*)x, (const uint16_t*)wpacked, bias, (uint16_t*)y, stats_partial, tiles,
-                         acfe_conv2d_stats_rows(g.M, K));
-      return launch_rc("acfe_conv2d_fwd_add(persistent)");
-    }
+    // k_conv3x3_cw with the residual epilogue (wr_resnet_bird's stage-2 / 3 branch2b)
+    const int rc = launch_cw<true>(g, x, wpacked, bias, y, stats_partial, gm, strm(stream), "acfe_conv2d_fwd_add(cw)");
+    if (rc != ACFE_E_INVAL) return rc;
+    if (fwd_p_ok(g, 128))  // the persistent GEMM with the residual epilogue (wr_resnet's stage 3)
+      return launch_fwd_p<128, true>(g, x, wpacked, bias, y, stats_partial, gm, strm(stream),
+                                     "acfe_conv2d_fwd_add(persistent)");
     hipLaunchKernelGGL((k_conv_fwd_g<uint16_t, 128, 128, 2, 2, true>), dim3(gm, ny), dim3(256), 0, strm(stream), g,
                        (const uint16_t*)x, (const uint16_t*)wpacked, bias, (uint16_t*)y, stats_partial, tiles_m);
     return launch_rc("acfe_conv2d_fwd_add(generic)");
   }
   ConvGeom g = make_geom(N, H, W, C, K, 3, 3, 1, pad_top, pad_left, H, W, 64, K);
-  g.res = (const uint16_t*)res;
-  g.res_relu = relu ? 1 : 0;
+  set_residual(g, res, relu);
   const int srows = grid_m_for(g.M, 1);
   if (K == 128)
     return launch_rows<128, 3>(g, x, wpacked, bias, y, stats_partial, srows, nullptr, strm(stream),
@@ -5101,10 +5029,7 @@ ACFE_API int acfe_conv2d_fwd_bn(const void* x, int N, int H, int W, int C, const
     return ACFE_E_INVAL;
   ConvGeom g = make_geom(N, H, W, C, K, 3, 3, 1, pad_top, pad_left, H, W, 64, K);
   g.drop = make_drop(drop_rate, seed);
-  g.pro_sc = bn_scale;
-  g.pro_sh = bn_shift;
-  g.pro_relu = bn_relu ? 1 : 0;
-  g.pro_out = (uint16_t*)x_bn_out;
+  set_prologue(g, bn_scale, bn_shift, bn_relu, x_bn_out);
   const int srows = grid_m_for(g.M, 1);
   if (K == 128) return launch_plain1w(g, x, wpacked, bias, y, stats_partial, srows, strm(stream), "acfe_conv2d_fwd_bn", 0);
   if (g.drop.on)
@@ -5162,10 +5087,7 @@ ACFE_API int acfe_conv2d_fwd_bn_keep(const void* x, int N, int H, int W, int C, 
     return ACFE_E_INVAL;
   ConvGeom g = make_geom(N, H, W, C, K, 3, 3, 1, pad_top, pad_left, H, W, 64, K);
   g.drop = make_drop(drop_rate, seed);
-  g.pro_sc = bn_scale;
-  g.pro_sh = bn_shift;
-  g.pro_relu = bn_relu ? 1 : 0;
-  g.pro_out = (uint16_t*)x_bn_out;
+  set_prologue(g, bn_scale, bn_shift, bn_relu, x_bn_out);
   return keep_launch(g, x, wpacked, bias, y, stats_partial, keep, strm(stream), "acfe_conv2d_fwd_bn_keep");
 }
 
@@ -5178,12 +5100,8 @@ ACFE_API int acfe_conv2d_fwd_add_bn(const void* x, int N, int H, int W, int C, c
       ((uintptr_t)res & 7))
     return ACFE_E_INVAL;
   ConvGeom g = make_geom(N, H, W, C, K, 3, 3, 1, pad_top, pad_left, H, W, 64, K);
-  g.res = (const uint16_t*)res;
-  g.res_relu = relu ? 1 : 0;
-  g.pro_sc = bn_scale;
-  g.pro_sh = bn_shift;
-  g.pro_relu = bn_relu ? 1 : 0;
-  g.pro_out = (uint16_t*)x_bn_out;
+  set_residual(g, res, relu);
+  set_prologue(g, bn_scale, bn_shift, bn_relu, x_bn_out);
   const int srows = grid_m_for(g.M, 1);
   if (K == 128)
     return launch_plain1w(g, x, wpacked, bias, y, stats_partial, srows, strm(stream), "acfe_conv2d_fwd_add_bn", 3);
@@ -5191,827 +5109,3 @@ ACFE_API int acfe_conv2d_fwd_add_bn(const void* x, int N, int H, int W, int C, c
                             "acfe_conv2d_fwd_add_bn");
 }
 
-// ------------------------------------------------------------------ stem (C = 1)
-// y[n,h,w,k] = sum_{r,s} x[n, h - pt + r, w - pl + s] * weff[k][r][s] + b[k]
-// (stride 1, P = H, Q = W).  Tile: 16 rows x 64 cols; thread = one column x
-// 4 rows (lane = column, so LDS reads of consecutive lanes are consecutive
-// words or 32 B pixels: conflict-free).  The 16 x R x S weights are read
-// with wave-uniform indices (scalar loads), all R x S x 16 taps unrolled.
-constexpr int STEM_TH = 16, STEM_TW = 64, STEM_K = 16, STEM_MAXR = 7, STEM_CAP = 2048;
-
-// 16 channels of one pixel (32 B bf16 / 64 B fp32) from LDS -> fp32
-__device__ __forceinline__ void unpack16(const uint16_t* p, float* f) {
-  const u32x4 a = *reinterpret_cast<const u32x4*>(p), b = *reinterpret_cast<const u32x4*>(p + 8);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __uint_as_float(a[i] << 16);
-    f[2 * i + 1] = __uint_as_float(a[i] & 0xffff0000u);
-    f[8 + 2 * i] = __uint_as_float(b[i] << 16);
-    f[8 + 2 * i + 1] = __uint_as_float(b[i] & 0xffff0000u);
-  }
-}
-__device__ __forceinline__ void unpack16(const float* p, float* f) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const f4 v = *reinterpret_cast<const f4*>(p + 4 * i);
-    f[4 * i] = v[0]; f[4 * i + 1] = v[1]; f[4 * i + 2] = v[2]; f[4 * i + 3] = v[3];
-  }
-}
-__device__ __forceinline__ void store16(uint16_t* d, const float* f) {
-  u32x4 a, b;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    a[i] = (unsigned)f2bf(f[2 * i]) | ((unsigned)f2bf(f[2 * i + 1]) << 16);
-    b[i] = (unsigned)f2bf(f[8 + 2 * i]) | ((unsigned)f2bf(f[8 + 2 * i + 1]) << 16);
-  }
-  *reinterpret_cast<u32x4*>(d) = a;
-  *reinterpret_cast<u32x4*>(d + 8) = b;
-}
-__device__ __forceinline__ void store16(float* d, const float* f) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f4 v = {f[4 * i], f[4 * i + 1], f[4 * i + 2], f[4 * i + 3]};
-    *reinterpret_cast<f4*>(d + 4 * i) = v;
-  }
-}
-
-// x halo tile (single channel) -> fp32 LDS, zero outside the image.
-template <typename TI, int XH, int XW>
-__device__ __forceinline__ void stem_load_x(const TI* __restrict__ x, int n, int H, int W, int gh0, int gw0,
-                                            float* xs) {
-  for (int i = threadIdx.x; i < XH * XW; i += 256) {
-    const int yy = i / XW, xx = i - (i / XW) * XW;
-    const int h = gh0 + yy, w = gw0 + xx;
-    float v = 0.f;
-    if ((unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W) v = to_f(x[((long long)n * H + h) * W + w]);
-    xs[i] = v;
-  }
-}
-
-// Folded weights are laid out weff[r][s][k] (RSK): the 16 weights of one tap
-// are one 64 B scalar load, used as SGPR operands of v_fmac.
-template <typename TI, typename TO, int R, int S>
-__global__ void __launch_bounds__(256)
-k_stem_fwd(const TI* __restrict__ x, int N, int H, int W, int pt, int pl,
-           const float* __restrict__ weff, const float* __restrict__ bias, TO* __restrict__ y,
-           double* __restrict__ stats, int tiles_h, int tiles_w) {
-  constexpr int XH = STEM_TH + R - 1, XW = STEM_TW + S - 1, RH = 4 + R - 1;
-  __shared__ float xs[XH * XW];
-  __shared__ double red[4][2][STEM_K];
-  const int tid = threadIdx.x, ox = tid & 63, q = tid >> 6;
-  const long long ntiles = (long long)N * tiles_h * tiles_w;
-  double s1[STEM_K], s2[STEM_K];
-#pragma unroll
-  for (int k = 0; k < STEM_K; ++k) s1[k] = 0.0, s2[k] = 0.0;
-  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const int tw = (int)(t % tiles_w);
-    const int th = (int)((t / tiles_w) % tiles_h);
-    const int n = (int)(t / ((long long)tiles_w * tiles_h));
-    const int h0 = th * STEM_TH, w0 = tw * STEM_TW;
-    __syncthreads();
-    stem_load_x<TI, XH, XW>(x, n, H, W, h0 - pt, w0 - pl, xs);
-    __syncthreads();
-    float acc[4][STEM_K];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int k = 0; k < STEM_K; ++k) acc[j][k] = bias ? bias[k] : 0.f;
-    // column s of the thread's halo: RH values; output row j uses halo row j + r
-#pragma unroll 1
-    for (int s = 0; s < S; ++s) {
-      float xc[RH];
-#pragma unroll
-      for (int i = 0; i < RH; ++i) xc[i] = xs[(4 * q + i) * XW + ox + s];
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const float* wt = weff + (r * S + s) * STEM_K;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int k = 0; k < STEM_K; ++k) acc[j][k] += xc[j + r] * wt[k];
-      }
-    }
-    const int w = w0 + ox;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int h = h0 + 4 * q + j;
-      if (h < H && w < W) {
-        float o[STEM_K];
-#pragma unroll
-        for (int k = 0; k < STEM_K; ++k) o[k] = to_f(cvt_out(acc[j][k], TO()));  // stats of stored values
-        store16(y + (((long long)n * H + h) * W + w) * STEM_K, o);
-        if (stats) {
-#pragma unroll
-          for (int k = 0; k < STEM_K; ++k) s1[k] += o[k], s2[k] += (double)o[k] * o[k];
-        }
-      }
-    }
-  }
-  if (stats) {
-    const int lane = tid & 63, wid = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < STEM_K; ++k) {
-      const double a = wave_sumd(s1[k]), b = wave_sumd(s2[k]);
-      if (lane == 0) red[wid][0][k] = a, red[wid][1][k] = b;
-    }
-    __syncthreads();
-    if (tid < 2 * STEM_K) {
-      const int which = tid / STEM_K, k = tid % STEM_K;
-      stats[((long long)blockIdx.x * 2 + which) * STEM_K + k] =
-          red[0][which][k] + red[1][which][k] + red[2][which][k] + red[3][which][k];
-    }
-  }
-}
-
-// dx[n,h,w] = sum_{k,r,s} dy[n, h + pt - r, w + pl - s, k] * weff[r][s][k]
-// dy halo tile kept pixel-major in LDS (16 channels = 32 B per pixel, copied
-// with 16 B loads/stores); one tile per block.  Per halo column the thread
-// holds its RH x 16 dy values in registers and applies all R taps of that
-// column to its 4 output rows.
-template <typename TG, typename TO, int R, int S>
-__global__ void __launch_bounds__(256)
-k_stem_dgrad(const TG* __restrict__ dy, int N, int H, int W, int pt, int pl,
-             const float* __restrict__ weff, TO* __restrict__ dx, int tiles_h, int tiles_w) {
-  constexpr int XH = STEM_TH + R - 1, XW = STEM_TW + S - 1, RH = 4 + R - 1;
-  constexpr int CPP = STEM_K * (int)sizeof(TG) / 16;  // 16 B chunks per pixel
-  __shared__ __attribute__((aligned(16))) TG gs[XH * XW * STEM_K];
-  const int tid = threadIdx.x, ox = tid & 63, q = tid >> 6;
-  const long long t = blockIdx.x;
-  const int tw = (int)(t % tiles_w);
-  const int th = (int)((t / tiles_w) % tiles_h);
-  const int n = (int)(t / ((long long)tiles_w * tiles_h));
-  const int h0 = th * STEM_TH, w0 = tw * STEM_TW;
-  const int gh0 = h0 - (R - 1 - pt), gw0 = w0 - (S - 1 - pl);
-  for (int i = tid; i < XH * XW * CPP; i += 256) {
-    const int pos = i / CPP, c = i - (i / CPP) * CPP;
-    const int yy = pos / XW, xx = pos - (pos / XW) * XW;
-    const int h = gh0 + yy, w = gw0 + xx;
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if ((unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W)
-      v = *reinterpret_cast<const u32x4*>(dy + (((long long)n * H + h) * W + w) * STEM_K + c * (16 / (int)sizeof(TG)));
-    *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned char*>(gs) + (long long)i * 16) = v;
-  }
-  __syncthreads();
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  // halo row 4q + i, col ox + cc holds dy for output row j with r = j + R-1-i, s = S-1-cc
-#pragma unroll 1
-  for (int cc = 0; cc < S; ++cc) {
-    float g[RH][STEM_K];
-#pragma unroll
-    for (int i = 0; i < RH; ++i) unpack16(gs + ((4 * q + i) * XW + ox + cc) * STEM_K, g[i]);
-    const int s = S - 1 - cc;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const float* wt = weff + (r * S + s) * STEM_K;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int k = 0; k < STEM_K; ++k) acc[j] += g[j + R - 1 - r][k] * wt[k];
-    }
-  }
-  const int w = w0 + ox;
-  if (w < W) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int h = h0 + 4 * q + j;
-      if (h < H) dx[((long long)n * H + h) * W + w] = cvt_out(acc[j], TO());
-    }
-  }
-}
-
-// dweff[k][r][s] partials per block: thread -> (column ox = lane, channels
-// 4*kq .. 4*kq+3 with kq = wave), R*S*4 fp32 accumulators over the block's
-// tiles, reduced across the wave in double at the end.  The x window of the
-// thread (R rows x S cols) slides down the tile in registers.
-template <typename TI, typename TG, int R, int S>
-__global__ void __launch_bounds__(256)
-k_stem_wgrad(const TI* __restrict__ x, const TG* __restrict__ dy, int N, int H, int W, int pt,
-             int pl, double* __restrict__ part, int tiles_h, int tiles_w) {
-  constexpr int XH = STEM_TH + R - 1, XW = STEM_TW + S - 1;
-  __shared__ float xs[XH * XW];
-  const int tid = threadIdx.x, ox = tid & 63, kq = tid >> 6;
-  float acc[4][R * S];
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-    for (int i = 0; i < R * S; ++i) acc[kk][i] = 0.f;
-  const long long ntiles = (long long)N * tiles_h * tiles_w;
-  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const int tw = (int)(t % tiles_w);
-    const int th = (int)((t / tiles_w) % tiles_h);
-    const int n = (int)(t / ((long long)tiles_w * tiles_h));
-    const int h0 = th * STEM_TH, w0 = tw * STEM_TW;
-    __syncthreads();
-    stem_load_x<TI, XH, XW>(x, n, H, W, h0 - pt, w0 - pl, xs);
-    __syncthreads();
-    const int w = w0 + ox;
-    float win[R][S];
-#pragma unroll
-    for (int r = 0; r < R - 1; ++r)
-#pragma unroll
-      for (int s = 0; s < S; ++s) win[r + 1][s] = xs[r * XW + ox + s];
-#pragma unroll 1
-    for (int oy = 0; oy < STEM_TH; ++oy) {
-#pragma unroll
-      for (int r = 0; r < R - 1; ++r)
-#pragma unroll
-        for (int s = 0; s < S; ++s) win[r][s] = win[r + 1][s];
-#pragma unroll
-      for (int s = 0; s < S; ++s) win[R - 1][s] = xs[(oy + R - 1) * XW + ox + s];
-      const int h = h0 + oy;
-      float g[4] = {0.f, 0.f, 0.f, 0.f};
-      if (h < H && w < W) {
-        const TG* gp = dy + (((long long)n * H + h) * W + w) * STEM_K + 4 * kq;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) g[kk] = to_f(gp[kk]);
-      }
-#pragma unroll
-      for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int s = 0; s < S; ++s)
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) acc[kk][r * S + s] += g[kk] * win[r][s];
-    }
-  }
-  const int lane = tid & 63;
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-    for (int i = 0; i < R * S; ++i) {
-      const double v = wave_sumd((double)acc[kk][i]);
-      if (lane == 0) part[(long long)blockIdx.x * STEM_K * R * S + (4 * kq + kk) * R * S + i] = v;
-    }
-}
-
-// dweff partials [blocks][k][r][s] -> dw[k][r][s][rep] (+beta*dw); one block per tap.
-__global__ void k_stem_wgrad_reduce(const double* __restrict__ part, int np, int n, int rep, float beta,
-                                    float* __restrict__ dw) {
-  __shared__ double red[4];
-  const int i = blockIdx.x;
-  double s = 0.0;
-  for (int j = threadIdx.x; j < np; j += 256) s += part[(long long)j * n + i];
-  s = wave_sumd(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x < rep) {
-    const double tot = red[0] + red[1] + red[2] + red[3];
-    float* d = dw + (long long)i * rep + threadIdx.x;
-    *d = beta != 0.f ? *d * beta + (float)tot : (float)tot;
-  }
-}
-
-// weff[r][s][k] = sum_c w[k][r][s][c]  (folds the identical input channels)
-__global__ void k_stem_fold(const float* __restrict__ w, int K, int RS, int rep, float* __restrict__ weff) {
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < K * RS; i += gridDim.x * 256) {
-    const int k = i % K, rs = i / K;
-    float s = 0.f;
-    for (int c = 0; c < rep; ++c) s += w[((long long)k * RS + rs) * rep + c];
-    weff[i] = s;
-  }
-}
-
-// ---- MFMA stem (bf16 activations; R*S <= 32 taps) -------------------------
-// Same tiles (16 rows x 64 columns, grid-stride) and slab contracts as the
-// VALU kernels above; the 5x5 taps become the 32-deep reduction of
-// v_mfma_f32_16x16x32_bf16 (zero-padded from 25), so the VALU work per pixel
-// is an LDS gather instead of 400 FMAs:
-//   fwd:   D[k][px] = sum_t weff[t][k] * x[px + off_t]      (A = weights, B = im2col gather)
-//   dgrad: D[.][px] = sum_{t,k} dy[px - off_t][k] weff[t][k] (B = 16-B dy reads, 2 taps x 16
-//          channels per k-step; the A rows are replicated, one row is the result)
-//   wgrad: D[k][t]  = sum_px dy[px][k] * x[px + off_t]      (A = dy chunk read transposed,
-//          B = im2col gather; k-dimension = 32 pixels of one row)
-// Weights are bf16 (the VALU kernels keep fp32 weights: the fp32 path).
-typedef __attribute__((address_space(3))) bf4* stem_lp;
-
-__device__ __forceinline__ unsigned stem_pack2(float a, float b) {
-  return (unsigned)f2bf(a) | ((unsigned)f2bf(b) << 16);
-}
-
-template <int R, int S>
-__global__ void __launch_bounds__(256)
-k_stem_fwd_mfma(const uint16_t* __restrict__ x, int N, int H, int W, int pt, int pl, const float* __restrict__ weff,
-                const float* __restrict__ bias, uint16_t* __restrict__ y, double* __restrict__ stats, int tiles_h,
-                int tiles_w) {
-  constexpr int XH = STEM_TH + R - 1, XW = STEM_TW + S - 1, NT = R * S;
-  static_assert(NT <= 32, "taps");
-  __shared__ uint16_t xs[XH * XW];
-  __shared__ double red[2][STEM_K];
-  const int tid = threadIdx.x, lane = tid & 63, l16 = lane & 15, q = lane >> 4, wid = tid >> 6;
-  for (int i = tid; i < 2 * STEM_K; i += 256) (&red[0][0])[i] = 0.0;
-  uint4 wa;
-  int toff[8];
-  {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int t = q * 8 + j;
-      v[j] = t < NT ? weff[t * STEM_K + l16] : 0.f;
-      toff[j] = t < NT ? (t / S) * XW + (t % S) : 0;
-    }
-    wa = uint4{stem_pack2(v[0], v[1]), stem_pack2(v[2], v[3]), stem_pack2(v[4], v[5]), stem_pack2(v[6], v[7])};
-  }
-  float bk[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) bk[r] = bias ? bias[q * 4 + r] : 0.f;
-  double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
-  const long long ntiles = (long long)N * tiles_h * tiles_w;
-  for (long long tt = blockIdx.x; tt < ntiles; tt += gridDim.x) {
-    const int tw = (int)(tt % tiles_w), th = (int)((tt / tiles_w) % tiles_h);
-    const int n = (int)(tt / ((long long)tiles_w * tiles_h));
-    const int h0 = th * STEM_TH, w0 = tw * STEM_TW;
-    __syncthreads();
-    for (int i = tid; i < XH * XW; i += 256) {
-      const int yy = i / XW, xx = i - yy * XW;
-      const int h = h0 - pt + yy, w = w0 - pl + xx;
-      xs[i] = ((unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W) ? x[((long long)n * H + h) * W + w] : 0;
-    }
-    __syncthreads();
-#pragma unroll 2
-    for (int blk = 0; blk < 16; ++blk) {
-      const int ry = wid * 4 + (blk >> 2), cx = (blk & 3) * 16 + l16;
-      const uint16_t* src = xs + ry * XW + cx;
-      unsigned tv[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) tv[j] = (q * 8 + j < NT) ? src[toff[j]] : 0u;
-      const uint4 b = uint4{tv[0] | (tv[1] << 16), tv[2] | (tv[3] << 16), tv[4] | (tv[5] << 16), tv[6] | (tv[7] << 16)};
-      const f4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8, wa), __builtin_bit_cast(bf8, b),
-                                                             f4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-      const int h = h0 + ry, w = w0 + cx;
-      if (h < H && w < W) {
-        float o[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[r] = bf2f(f2bf(acc[r] + bk[r]));
-        *reinterpret_cast<uint2*>(y + (((long long)n * H + h) * W + w) * STEM_K + q * 4) =
-            uint2{stem_pack2(o[0], o[1]), stem_pack2(o[2], o[3])};
-        if (stats) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) s1[r] += o[r], s2[r] += (double)o[r] * o[r];
-        }
-      }
-    }
-  }
-  if (stats) {
-    // lanes with the same q hold the same 4 channels: reduce over l16
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int o = 8; o > 0; o >>= 1) {
-        s1[r] += __shfl_xor(s1[r], o, 64);
-        s2[r] += __shfl_xor(s2[r], o, 64);
-      }
-    }
-    __syncthreads();
-    if (l16 == 0) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        atomicAdd(&red[0][q * 4 + r], s1[r]);
-        atomicAdd(&red[1][q * 4 + r], s2[r]);
-      }
-    }
-    __syncthreads();
-    if (tid < 2 * STEM_K) stats[(long long)blockIdx.x * 2 * STEM_K + tid] = (&red[0][0])[tid];
-  }
-}
-
-template <int R, int S>
-__global__ void __launch_bounds__(256)
-k_stem_dgrad_mfma(const uint16_t* __restrict__ dy, int N, int H, int W, int pt, int pl,
-                  const float* __restrict__ weff, uint16_t* __restrict__ dx, int tiles_h, int tiles_w) {
-  constexpr int XH = STEM_TH + R - 1, XW = STEM_TW + S - 1, NT = R * S, NKT = (NT + 1) / 2;
-  __shared__ __attribute__((aligned(16))) uint16_t gs[XH * XW * STEM_K];
-  const int tid = threadIdx.x, lane = tid & 63, l16 = lane & 15, q = lane >> 4, wid = tid >> 6;
-  // k-step kt: k-slot q*8 + j <-> (tap 2kt + (q >> 1), channel (q & 1)*8 + j); A rows replicated
-  uint4 wa[NKT];
-  int goff[NKT];
-#pragma unroll
-  for (int kt = 0; kt < NKT; ++kt) {
-    const int t = 2 * kt + (q >> 1), r = t / S, s = t % S;
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = t < NT ? weff[t * STEM_K + (q & 1) * 8 + j] : 0.f;
-    wa[kt] = uint4{stem_pack2(v[0], v[1]), stem_pack2(v[2], v[3]), stem_pack2(v[4], v[5]), stem_pack2(v[6], v[7])};
-    goff[kt] = t < NT ? ((R - 1 - r) * XW + (S - 1 - s)) * STEM_K + (q & 1) * 8 : -1;
-  }
-  const uint4 z4 = {0u, 0u, 0u, 0u};
-  const long long ntiles = (long long)N * tiles_h * tiles_w;
-  for (long long tt = blockIdx.x; tt < ntiles; tt += gridDim.x) {
-    const int tw = (int)(tt % tiles_w), th = (int)((tt / tiles_w) % tiles_h);
-    const int n = (int)(tt / ((long long)tiles_w * tiles_h));
-    const int h0 = th * STEM_TH, w0 = tw * STEM_TW;
-    const int gh0 = h0 - (R - 1 - pt), gw0 = w0 - (S - 1 - pl);
-    __syncthreads();
-    for (int i = tid; i < XH * XW * 2; i += 256) {
-      const int pos = i >> 1, c = i & 1;
-      const int yy = pos / XW, xx = pos - yy * XW;
-      const int h = gh0 + yy, w = gw0 + xx;
-      u32x4 v = {0u, 0u, 0u, 0u};
-      if ((unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W)
-        v = *reinterpret_cast<const u32x4*>(dy + (((long long)n * H + h) * W + w) * STEM_K + c * 8);
-      *reinterpret_cast<u32x4*>(gs + (long long)i * 8) = v;
-    }
-    __syncthreads();
-#pragma unroll 2
-    for (int blk = 0; blk < 16; ++blk) {
-      const int ry = wid * 4 + (blk >> 2), cx = (blk & 3) * 16 + l16;
-      const uint16_t* base = gs + (ry * XW + cx) * STEM_K;
-      f4 acc = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt) {
-        const uint4 b = goff[kt] >= 0 ? *reinterpret_cast<const uint4*>(base + goff[kt]) : z4;
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8, wa[kt]), __builtin_bit_cast(bf8, b), acc,
-                                                      0, 0, 0);
-      }
-      const int h = h0 + ry, w = w0 + cx;
-      if (q == 0 && h < H && w < W) dx[((long long)n * H + h) * W + w] = f2bf(acc[0]);
-    }
-  }
-}
-
-template <int R, int S>
-__global__ void __launch_bounds__(256)
-k_stem_wgrad_mfma(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dy, int N, int H, int W, int pt,
-                  int pl, double* __restrict__ part, int tiles_h, int tiles_w) {
-  constexpr int XH = STEM_TH + R - 1, XW = STEM_TW + S - 1, NT = R * S, LDG = 24;
-  __shared__ uint16_t xs[XH * XW];
-  __shared__ __attribute__((aligned(16))) uint16_t gch[4][32 * LDG];  // per wave: 32 px x 16 ch of dy
-  __shared__ float red[4][STEM_K][32];
-  const int tid = threadIdx.x, lane = tid & 63, l16 = lane & 15, q = lane >> 4, wid = tid >> 6;
-  const int grp = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3;
-  // B k-slot (q, j) <-> chunk pixel j<4: 4q+j, else 16+4q+(j-4) (the transposed-read order)
-  int tof0, tof1;
-  {
-    const int t0 = l16, t1 = 16 + l16;
-    tof0 = t0 < NT ? (t0 / S) * XW + (t0 % S) : -1;
-    tof1 = t1 < NT ? (t1 / S) * XW + (t1 % S) : -1;
-  }
-  f4 d0 = f4{0.f, 0.f, 0.f, 0.f}, d1 = d0;
-  uint16_t* gw = gch[wid];
-  const long long ntiles = (long long)N * tiles_h * tiles_w;
-  for (long long tt = blockIdx.x; tt < ntiles; tt += gridDim.x) {
-    const int tw = (int)(tt % tiles_w), th = (int)((tt / tiles_w) % tiles_h);
-    const int n = (int)(tt / ((long long)tiles_w * tiles_h));
-    const int h0 = th * STEM_TH, w0 = tw * STEM_TW;
-    __syncthreads();
-    for (int i = tid; i < XH * XW; i += 256) {
-      const int yy = i / XW, xx = i - yy * XW;
-      const int h = h0 - pt + yy, w = w0 - pl + xx;
-      xs[i] = ((unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W) ? x[((long long)n * H + h) * W + w] : 0;
-    }
-    __syncthreads();
-    for (int c = 0; c < 8; ++c) {  // the wave's 4 rows x 64 columns in 32-pixel chunks
-      const int ry = wid * 4 + (c >> 1), cx0 = (c & 1) * 32;
-      const int h = h0 + ry;
-      {
-        const int px = lane >> 1, half = lane & 1, w = w0 + cx0 + px;
-        u32x4 v = {0u, 0u, 0u, 0u};
-        if (h < H && w < W)
-          v = *reinterpret_cast<const u32x4*>(dy + (((long long)n * H + h) * W + w) * STEM_K + half * 8);
-        *reinterpret_cast<u32x4*>(gw + px * LDG + half * 8) = v;
-      }
-      const bf4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-          (stem_lp)(reinterpret_cast<const __bf16*>(gw + (4 * grp + qq) * LDG + 4 * pp)));
-      const bf4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-          (stem_lp)(reinterpret_cast<const __bf16*>(gw + (16 + 4 * grp + qq) * LDG + 4 * pp)));
-      const bf8 a = bf8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      const uint16_t* src = xs + ry * XW + cx0;
-      unsigned b0[8], b1[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int px = j < 4 ? 4 * q + j : 16 + 4 * q + (j - 4);
-        b0[j] = tof0 >= 0 ? src[px + tof0] : 0u;
-        b1[j] = tof1 >= 0 ? src[px + tof1] : 0u;
-      }
-      const uint4 B0 = uint4{b0[0] | (b0[1] << 16), b0[2] | (b0[3] << 16), b0[4] | (b0[5] << 16), b0[6] | (b0[7] << 16)};
-      const uint4 B1 = uint4{b1[0] | (b1[1] << 16), b1[2] | (b1[3] << 16), b1[4] | (b1[5] << 16), b1[6] | (b1[7] << 16)};
-      d0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(bf8, B0), d0, 0, 0, 0);
-      d1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(bf8, B1), d1, 0, 0, 0);
-    }
-  }
-  // D lane: row k = q*4 + r, column t = l16 (+16)
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    red[wid][q * 4 + r][l16] = d0[r];
-    red[wid][q * 4 + r][16 + l16] = d1[r];
-  }
-  __syncthreads();
-  for (int i = tid; i < STEM_K * NT; i += 256) {
-    const int k = i / NT, t = i - k * NT;
-    part[(long long)blockIdx.x * STEM_K * NT + i] =
-        ((double)red[0][k][t] + (double)red[1][k][t]) + ((double)red[2][k][t] + (double)red[3][k][t]);
-  }
-}
-
-
-// ------------------------------------------------------------------ stem backward with the BN backward apply
-// wr_resnet_bird's stem conv1_1 (5 x 5, 16 filters, bias) -> BatchNormalization
-// -> MaxPool2D((1, 2)) (resnet/wr_resnet_bird.py:22-30).  The BN backward's
-// elementwise pass dX_bn = a*g*[x*scale+shift > 0] + b*x + c (k_bn_bwd_apply8:
-// reads g and x, writes dX_bn, 3 x 1.07 GB per T1 step) is formed while the
-// stem dgrad stages its dY halo; the weight gradient and the conv-bias sums
-// read the same LDS image, so dX_bn is never stored and the separate wgrad's
-// re-read of it is gone.  dX bit-identical to the apply8 -> k_stem_dgrad_mfma
-// chain (the same bf16 dX_bn and MFMA operands); dW the k_stem_wgrad_mfma
-// arithmetic over stem_bwd_grid's workgroups (its fp32 partials summed in
-// another grouping than acfe_stem_wgrad's); bias sums [block][2][16] of the
-// bf16 dX_bn values over each tile's own pixels.
-template <int R, int S>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3)))
-k_stem_bwd_bn(const uint16_t* __restrict__ g, const uint16_t* __restrict__ xb, const uint16_t* __restrict__ xin,
-              int N, int H, int W, int pt, int pl, const float* __restrict__ weff, const float* __restrict__ scale,
-              const float* __restrict__ shift, const float* __restrict__ coef, int relu, uint16_t* __restrict__ dxin,
-              double* __restrict__ wpart, double* __restrict__ bpart, int tiles_h, int tiles_w) {
-  constexpr int XH = STEM_TH + R - 1, XW = STEM_TW + S - 1, NT = R * S, NKT = (NT + 1) / 2;
-  constexpr int GSZ = XH * XW * STEM_K;
-  static_assert(GSZ * 2 >= 4 * STEM_K * 32 * 4, "the wgrad reduction aliases the dY image");
-  __shared__ __attribute__((aligned(16))) uint16_t gs[GSZ];
-  __shared__ uint16_t xs[XH * XW];
-  __shared__ double bred[4][STEM_K];
-  __shared__ __attribute__((aligned(16))) float bnc[5][STEM_K];  // scale, shift, coef a, b, c
-  const int tid = threadIdx.x, lane = tid & 63, l16 = lane & 15, q = lane >> 4, wid = tid >> 6;
-  if (tid < 5 * STEM_K) {
-    const int a = tid / STEM_K, k = tid - a * STEM_K;
-    bnc[a][k] = a == 0 ? scale[k] : (a == 1 ? shift[k] : coef[(a - 2) * STEM_K + k]);
-  }
-  // dgrad A operand (k_stem_dgrad_mfma): flipped folded weights, k-slot q*8 + j <-> (tap 2kt + (q >> 1), ch (q & 1)*8 + j)
-  uint4 wa[NKT];
-  int goff[NKT];
-#pragma unroll
-  for (int kt = 0; kt < NKT; ++kt) {
-    const int t = 2 * kt + (q >> 1), r = t / S, s = t % S;
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = t < NT ? weff[t * STEM_K + (q & 1) * 8 + j] : 0.f;
-    wa[kt] = uint4{stem_pack2(v[0], v[1]), stem_pack2(v[2], v[3]), stem_pack2(v[4], v[5]), stem_pack2(v[6], v[7])};
-    goff[kt] = t < NT ? ((R - 1 - r) * XW + (S - 1 - s)) * STEM_K + (q & 1) * 8 : -1;
-  }
-  // wgrad B operand (k_stem_wgrad_mfma): tap of column l16 / 16 + l16
-  const int grp = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3;
-  int tof0, tof1;
-  {
-    const int t0 = l16, t1 = 16 + l16;
-    tof0 = t0 < NT ? (t0 / S) * XW + (t0 % S) : -1;
-    tof1 = t1 < NT ? (t1 / S) * XW + (t1 % S) : -1;
-  }
-  // this thread's 8 staging channels: its index parity
-  const int c8 = (tid & 1) * 8;
-  double s1[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) s1[j] = 0.0;
-  f4 d0 = f4{0.f, 0.f, 0.f, 0.f}, d1 = d0;
-  const uint4 z4 = {0u, 0u, 0u, 0u};
-  const long long ntiles = (long long)N * tiles_h * tiles_w;
-  for (long long tt = blockIdx.x; tt < ntiles; tt += gridDim.x) {
-    const int tw = (int)(tt % tiles_w), th = (int)((tt / tiles_w) % tiles_h);
-    const int n = (int)(tt / ((long long)tiles_w * tiles_h));
-    const int h0 = th * STEM_TH, w0 = tw * STEM_TW;
-    const int gh0 = h0 - (R - 1 - pt), gw0 = w0 - (S - 1 - pl);
-    __syncthreads();
-    for (int i = tid; i < XH * XW * 2; i += 256) {
-      const int pos = i >> 1;
-      const int yy = pos / XW, xx = pos - yy * XW;
-      const int h = gh0 + yy, w = gw0 + xx;
-      u32x4 v = {0u, 0u, 0u, 0u};
-      if ((unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W) {
-        const long long e = (((long long)n * H + h) * W + w) * STEM_K + c8;
-        const u32x4 gv = *reinterpret_cast<const u32x4*>(g + e);
-        const u32x4 xv = *reinterpret_cast<const u32x4*>(xb + e);
-        float o[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const unsigned gw = gv[j >> 1], xw = xv[j >> 1];
-          const float gf = __uint_as_float((j & 1) ? (gw & 0xffff0000u) : (gw << 16));
-          const float xf = __uint_as_float((j & 1) ? (xw & 0xffff0000u) : (xw << 16));
-          const float gj = (relu && !(xf * bnc[0][c8 + j] + bnc[1][c8 + j] > 0.f)) ? 0.f : gf;
-          o[j] = __builtin_fmaf(bnc[2][c8 + j], gj, __builtin_fmaf(bnc[3][c8 + j], xf, bnc[4][c8 + j]));  // as k_bn_bwd_apply8
-        }
-        v = u32x4{stem_pack2(o[0], o[1]), stem_pack2(o[2], o[3]), stem_pack2(o[4], o[5]), stem_pack2(o[6], o[7])};
-        if ((unsigned)(yy - (R - 1 - pt)) < (unsigned)STEM_TH && (unsigned)(xx - (S - 1 - pl)) < (unsigned)STEM_TW) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const unsigned vw = v[j >> 1];
-            s1[j] += (double)__uint_as_float((j & 1) ? (vw & 0xffff0000u) : (vw << 16));
-          }
-        }
-      }
-      *reinterpret_cast<u32x4*>(gs + (long long)i * 8) = v;
-    }
-    for (int i = tid; i < XH * XW; i += 256) {
-      const int yy = i / XW, xx = i - yy * XW;
-      const int h = h0 - pt + yy, w = w0 - pl + xx;
-      xs[i] = ((unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W) ? xin[((long long)n * H + h) * W + w] : 0;
-    }
-    __syncthreads();
-    // dX of the stem input (k_stem_dgrad_mfma)
-#pragma unroll 2
-    for (int blk = 0; blk < 16; ++blk) {
-      const int ry = wid * 4 + (blk >> 2), cx = (blk & 3) * 16 + l16;
-      const uint16_t* base = gs + (ry * XW + cx) * STEM_K;
-      f4 acc = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt) {
-        const uint4 b = goff[kt] >= 0 ? *reinterpret_cast<const uint4*>(base + goff[kt]) : z4;
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8, wa[kt]), __builtin_bit_cast(bf8, b), acc,
-                                                      0, 0, 0);
-      }
-      const int h = h0 + ry, w = w0 + cx;
-      if (q == 0 && h < H && w < W) dxin[((long long)n * H + h) * W + w] = f2bf(acc[0]);
-    }
-    // dW (k_stem_wgrad_mfma): dY^T chunks read from the tile's own pixels of the image
-    for (int c = 0; c < 8; ++c) {
-      const int ry = wid * 4 + (c >> 1), cx0 = (c & 1) * 32;
-      const uint16_t* gw = gs + ((ry + R - 1 - pt) * XW + cx0 + S - 1 - pl) * STEM_K;
-      const bf4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-          (stem_lp)(reinterpret_cast<const __bf16*>(gw + (4 * grp + qq) * STEM_K + 4 * pp)));
-      const bf4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-          (stem_lp)(reinterpret_cast<const __bf16*>(gw + (16 + 4 * grp + qq) * STEM_K + 4 * pp)));
-      const bf8 a = bf8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      const uint16_t* src = xs + ry * XW + cx0;
-      unsigned b0[8], b1[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int px = j < 4 ? 4 * q + j : 16 + 4 * q + (j - 4);
-        b0[j] = tof0 >= 0 ? src[px + tof0] : 0u;
-        b1[j] = tof1 >= 0 ? src[px + tof1] : 0u;
-      }
-      const uint4 B0 = uint4{b0[0] | (b0[1] << 16), b0[2] | (b0[3] << 16), b0[4] | (b0[5] << 16), b0[6] | (b0[7] << 16)};
-      const uint4 B1 = uint4{b1[0] | (b1[1] << 16), b1[2] | (b1[3] << 16), b1[4] | (b1[5] << 16), b1[6] | (b1[7] << 16)};
-      d0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(bf8, B0), d0, 0, 0, 0);
-      d1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(bf8, B1), d1, 0, 0, 0);
-    }
-  }
-  // bias sums: lanes of one parity hold the same 8 channels
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-#pragma unroll
-    for (int o = 2; o < 64; o <<= 1) s1[j] += __shfl_xor(s1[j], o, 64);
-  }
-  __syncthreads();  // last tile's image reads done: the wgrad reduction reuses it
-  float(*red)[STEM_K][32] = reinterpret_cast<float(*)[STEM_K][32]>(gs);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    red[wid][q * 4 + r][l16] = d0[r];
-    red[wid][q * 4 + r][16 + l16] = d1[r];
-  }
-  if (lane < 2) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) bred[wid][lane * 8 + j] = s1[j];
-  }
-  __syncthreads();
-  for (int i = tid; i < STEM_K * NT; i += 256) {
-    const int k = i / NT, t = i - k * NT;
-    wpart[(long long)blockIdx.x * STEM_K * NT + i] =
-        ((double)red[0][k][t] + (double)red[1][k][t]) + ((double)red[2][k][t] + (double)red[3][k][t]);
-  }
-  // row 1 of the [2][16] slab (sums of squares in the statistics layout) is not used by the channel sums
-  if (tid < 2 * STEM_K)
-    bpart[(long long)blockIdx.x * 2 * STEM_K + tid] =
-        tid < STEM_K ? (bred[0][tid] + bred[1][tid]) + (bred[2][tid] + bred[3][tid]) : 0.0;
-}
-
-ACFE_API int acfe_stem_blocks(int N, int H, int W) {
-  const long long t = (long long)N * ((H + STEM_TH - 1) / STEM_TH) * ((W + STEM_TW - 1) / STEM_TW);
-  return (int)(t < STEM_CAP ? t : STEM_CAP);
-}
-
-// weff[r][s][k] = sum_c w[k][r][s][c]  (folds the identical input channels)
-ACFE_API int acfe_stem_fold_weights(const float* w, int K, int R, int S, int C, float* weff, void* stream) {
-  if (!w || !weff || K != STEM_K || R > STEM_MAXR || S > STEM_MAXR || C <= 0) return ACFE_E_INVAL;
-  hipLaunchKernelGGL(k_stem_fold, dim3(cdiv(K * R * S, 256)), dim3(256), 0, strm(stream), w, K, R * S, C, weff);
-  return launch_rc("acfe_stem_fold_weights");
-}
-
-ACFE_API int acfe_stem_fwd(const void* x, int x_dtype, int N, int H, int W, int R, int S, int pad_top,
-                           int pad_left, const float* weff, const float* bias, void* y, int y_dtype,
-                           double* stats_partial, void* stream) {
-  if (!x || !weff || !y || N < 0 || H <= 0 || W <= 0 || R != S || (R != 5 && R != 3)) return ACFE_E_INVAL;
-  if (N == 0) return ACFE_OK;
-  const int th = (H + STEM_TH - 1) / STEM_TH, tw = (W + STEM_TW - 1) / STEM_TW;
-  const int grid = acfe_stem_blocks(N, H, W);
-#define SF1(TI, TO, RR)                                                                                      \
-  hipLaunchKernelGGL((k_stem_fwd<TI, TO, RR, RR>), dim3(grid), dim3(256), 0, strm(stream), (const TI*)x, N, H, W, \
-                     pad_top, pad_left, weff, bias, (TO*)y, stats_partial, th, tw)
-#define SF(TI, TO) if (R == 5) SF1(TI, TO, 5); else SF1(TI, TO, 3)
-  if (x_dtype == ACFE_DTYPE_BF16 && y_dtype == ACFE_DTYPE_BF16) {
-    // one resident round (7 workgroups per CU at 62 VGPRs) instead of 2048 in
-    // 1.14 rounds; the statistics slab rows past the grid are zeroed
-    const int g1 = grid < 7 * 256 ? grid : 7 * 256;
-    if (stats_partial && g1 < grid) {
-      const hipError_t e = hipMemsetAsync(stats_partial + (size_t)g1 * 2 * STEM_K, 0,
-                                          sizeof(double) * 2 * STEM_K * (grid - g1), strm(stream));
-      if (e != hipSuccess) return hip_rc(e, "acfe_stem_fwd");
-    }
-    if (R == 5)
-      hipLaunchKernelGGL((k_stem_fwd_mfma<5, 5>), dim3(g1), dim3(256), 0, strm(stream), (const uint16_t*)x, N, H, W,
-                         pad_top, pad_left, weff, bias, (uint16_t*)y, stats_partial, th, tw);
-    else
-      hipLaunchKernelGGL((k_stem_fwd_mfma<3, 3>), dim3(g1), dim3(256), 0, strm(stream), (const uint16_t*)x, N, H, W,
-                         pad_top, pad_left, weff, bias, (uint16_t*)y, stats_partial, th, tw);
-  } else if (x_dtype == ACFE_DTYPE_BF16 && y_dtype == ACFE_DTYPE_BF16) SF(uint16_t, uint16_t);
-  else if (x_dtype == ACFE_DTYPE_BF16) SF(uint16_t, float);
-  else if (y_dtype == ACFE_DTYPE_BF16) SF(float, uint16_t);
-  else SF(float, float);
-#undef SF
-  return launch_rc("acfe_stem_fwd");
-}
-
-ACFE_API int acfe_stem_dgrad(const void* dy, int dy_dtype, int N, int H, int W, int R, int S, int pad_top,
-                             int pad_left, const float* weff, void* dx, int dx_dtype, void* stream) {
-  if (!dy || !weff || !dx || N < 0 || R != S || (R != 5 && R != 3)) return ACFE_E_INVAL;
-  if (N == 0) return ACFE_OK;
-  const int th = (H + STEM_TH - 1) / STEM_TH, tw = (W + STEM_TW - 1) / STEM_TW;
-  const long long grid = (long long)N * th * tw;  // one tile per block
-#define SD1(TG, TO, RR)                                                                                      \
-  hipLaunchKernelGGL((k_stem_dgrad<TG, TO, RR, RR>), dim3(grid), dim3(256), 0, strm(stream), (const TG*)dy, N, H, \
-                     W, pad_top, pad_left, weff, (TO*)dx, th, tw)
-#define SD(TG, TO) if (R == 5) SD1(TG, TO, 5); else SD1(TG, TO, 3)
-  if (dy_dtype == ACFE_DTYPE_BF16 && dx_dtype == ACFE_DTYPE_BF16) {
-    const int g2 = acfe_stem_blocks(N, H, W);
-    if (R == 5)
-      hipLaunchKernelGGL((k_stem_dgrad_mfma<5, 5>), dim3(g2), dim3(256), 0, strm(stream), (const uint16_t*)dy, N, H,
-                         W, pad_top, pad_left, weff, (uint16_t*)dx, th, tw);
-    else
-      hipLaunchKernelGGL((k_stem_dgrad_mfma<3, 3>), dim3(g2), dim3(256), 0, strm(stream), (const uint16_t*)dy, N, H,
-                         W, pad_top, pad_left, weff, (uint16_t*)dx, th, tw);
-  } else if (dy_dtype == ACFE_DTYPE_BF16 && dx_dtype == ACFE_DTYPE_BF16) SD(uint16_t, uint16_t);
-  else if (dy_dtype == ACFE_DTYPE_BF16) SD(uint16_t, float);
-  else if (dx_dtype == ACFE_DTYPE_BF16) SD(float, uint16_t);
-  else SD(float, float);
-#undef SD
-  return launch_rc("acfe_stem_dgrad");
-}
-
-// Workgroups of k_stem_bwd_bn: one resident round (3 per CU: 168 VGPRs, 46 KB
-// of LDS) each walking its share of the tiles, instead of acfe_stem_blocks'
-// 2048 in 2.7 rounds.  <= acfe_stem_blocks, which sizes the workspaces.
-static int stem_bwd_grid(int N, int H, int W) {
-  static const int cap = getenv("ACFE_STEM_BWD_GRID") ? atoi(getenv("ACFE_STEM_BWD_GRID")) : 768;
-  const int nb = acfe_stem_blocks(N, H, W);
-  return cap > 0 && cap < nb ? cap : nb;
-}
-
-// workspace: double[acfe_stem_blocks(N,H,W) * 16 * R * S]
-ACFE_API int acfe_stem_wgrad(const void* x, int x_dtype, const void* dy, int dy_dtype, int N, int H, int W,
-                             int R, int S, int pad_top, int pad_left, int rep, float* dw, float beta,
-                             double* workspace, void* stream) {
-  if (!x || !dy || !dw || !workspace || N <= 0 || R != S || (R != 5 && R != 3) || rep <= 0) return ACFE_E_INVAL;
-  const int th = (H + STEM_TH - 1) / STEM_TH, tw = (W + STEM_TW - 1) / STEM_TW;
-  const int grid = acfe_stem_blocks(N, H, W);
-#define SW1(TI, TG, RR)                                                                                      \
-  hipLaunchKernelGGL((k_stem_wgrad<TI, TG, RR, RR>), dim3(grid), dim3(256), 0, strm(stream), (const TI*)x,        \
-                     (const TG*)dy, N, H, W, pad_top, pad_left, workspace, th, tw)
-#define SW(TI, TG) if (R == 5) SW1(TI, TG, 5); else SW1(TI, TG, 3)
-  if (x_dtype == ACFE_DTYPE_BF16 && dy_dtype == ACFE_DTYPE_BF16) {
-    if (R == 5)
-      hipLaunchKernelGGL((k_stem_wgrad_mfma<5, 5>), dim3(grid), dim3(256), 0, strm(stream), (const uint16_t*)x,
-                         (const uint16_t*)dy, N, H, W, pad_top, pad_left, workspace, th, tw);
-    else
-      hipLaunchKernelGGL((k_stem_wgrad_mfma<3, 3>), dim3(grid), dim3(256), 0, strm(stream), (const uint16_t*)x,
-                         (const uint16_t*)dy, N, H, W, pad_top, pad_left, workspace, th, tw);
-  } else if (x_dtype == ACFE_DTYPE_BF16 && dy_dtype == ACFE_DTYPE_BF16) SW(uint16_t, uint16_t);
-  else if (x_dtype == ACFE_DTYPE_BF16) SW(uint16_t, float);
-  else if (dy_dtype == ACFE_DTYPE_BF16) SW(float, uint16_t);
-  else SW(float, float);
-#undef SW
-  int rc = launch_rc("acfe_stem_wgrad");
-  if (rc) return rc;
-  const int n = STEM_K * R * S;
-  if (rep > 256) return ACFE_E_INVAL;
-  hipLaunchKernelGGL(k_stem_wgrad_reduce, dim3(n), dim3(256), 0, strm(stream), workspace, grid, n, rep, beta, dw);
-  return launch_rc("acfe_stem_wgrad(reduce)");
-}
-
-// The stem backward with the BN backward apply folded in (k_stem_bwd_bn): g =
-// the BN output gradient (bf16 [N][H][W][16], e.g. acfe_maxpool2d_bwd_argmax_bn's
-// dX), xb = the BN input (= the stem output), coef = acfe_bn_bwd_finalize_ex's
-// [3][16] coefficients.  dxin: the stem input gradient (bf16 [N][H][W]); dw: [16][R][S][rep] fp32 (beta as acfe_stem_wgrad); bias_part:
-// double[acfe_stem_blocks(N,H,W)][2][16] channel sums of dX_bn (for
-// acfe_channel_sum_finalize); workspace: double[acfe_stem_blocks(N,H,W) * 16 * R * S].
-ACFE_API int acfe_stem_bwd_bn(const void* g, const void* xb, const void* xin, int N, int H, int W, int R, int S,
-                              int pad_top, int pad_left, const float* weff, const float* scale, const float* shift,
-                              const float* coef, int relu, void* dxin, int rep, float* dw, float beta,
-                              double* bias_part, double* workspace, void* stream) {
-  if (!g || !xb || !xin || !weff || !scale || !shift || !coef || !dw || !bias_part || !workspace || N <= 0 ||
-      H <= 0 || W <= 0 || R != S || (R != 5 && R != 3) || rep <= 0 || rep > 256 || ((uintptr_t)g & 15) ||
-      ((uintptr_t)xb & 15))
-    return ACFE_E_INVAL;
-  const int th = (H + STEM_TH - 1) / STEM_TH, tw = (W + STEM_TW - 1) / STEM_TW;
-  const int nb = acfe_stem_blocks(N, H, W), grid = stem_bwd_grid(N, H, W);
-  if (grid < nb) {  // bias slab rows past the grid: zero
-    const hipError_t e =
-        hipMemsetAsync(bias_part + (size_t)grid * 2 * STEM_K, 0, sizeof(double) * 2 * STEM_K * (nb - grid), strm(stream));
-    if (e != hipSuccess) return hip_rc(e, "acfe_stem_bwd_bn");
-  }
-  uint16_t* dxo = (uint16_t*)dxin;
-  if (!dxo) return ACFE_E_INVAL;
-#define SB(RR)                                                                                                \
-  hipLaunchKernelGGL((k_stem_bwd_bn<RR, RR>), dim3(grid), dim3(256), 0, strm(stream), (const uint16_t*)g,        \
-                     (const uint16_t*)xb, (const uint16_t*)xin, N, H, W, pad_top, pad_left, weff, scale, shift, coef, \
-                     relu, dxo, workspace, bias_part, th, tw)
-  if (R == 5) SB(5); else SB(3);
-#undef SB
-  int rc = launch_rc("acfe_stem_bwd_bn");
-  if (rc) return rc;
-  const int n = STEM_K * R * S;
-  hipLaunchKernelGGL(k_stem_wgrad_reduce, dim3(n), dim3(256), 0, strm(stream), workspace, grid, n, rep, beta, dw);
-  return launch_rc("acfe_stem_bwd_bn(reduce)");
-}

@@ -1,6 +1,7 @@
 // Definitions shared by the convolution translation units (conv.hip,
-// pool1w.hip): vector types, the launch geometry, the XCD-aware tile walk and
-// the LDS-DMA / wait helpers.
+// stem.hip, pool1w.hip, rows64.hip): vector types, the storage-type
+// conversions, the launch geometry, the XCD-aware tile walk with its host-side
+// grid, and the LDS-DMA / wait helpers.
 #pragma once
 #include "common.h"
 
@@ -23,6 +24,11 @@ typedef __bf16 b2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned pk_bf2(float lo, float hi) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector((f2v){lo, hi}, b2v));
 }
+// fp32 <-> the storage type (bf16 as uint16_t, or fp32), selected by a tag argument
+__device__ __forceinline__ uint16_t cvt_out(float v, uint16_t) { return f2bf(v); }
+__device__ __forceinline__ float cvt_out(float v, float) { return v; }
+__device__ __forceinline__ float to_f(uint16_t v) { return bf2f(v); }
+__device__ __forceinline__ float to_f(float v) { return v; }
 
 struct ConvGeom {
   int N, H, W, C;    // input
@@ -107,6 +113,28 @@ struct TileWalk {
     }
   }
 };
+
+// The persistent grid of a tile-walking kernel (host side): one workgroup per
+// CU (256), never more than its nt tiles, a multiple of 8 from 64 up (the
+// XCD-chunked TileWalk) and -- each workgroup writing statistics slab row
+// blockIdx.x -- never more than the caller's srows slab rows when it has a slab
+// (narrow images have more tiles than 128-pixel slab rows).
+inline int tile_grid(long long nt, bool stats, int srows) {
+  int gp = 256;
+  if (gp > nt) gp = (int)nt;
+  if (gp >= 64) gp &= ~7;
+  if (stats && gp > srows) gp = srows;
+  return gp;
+}
+// The grids of a main launch over nt tiles and a remainder-column launch over
+// nte tiles (0: none) that writes the slab rows after the first one's (small
+// slabs: the second launch is left up to half of the rows).  false: the slab
+// has no row left for the second launch.
+inline bool tile_grid_pair(long long nt, long long nte, bool stats, int srows, int* gp, int* gpe) {
+  *gp = tile_grid(nt, stats, nte && stats ? srows - (int)(srows / 2 < nte ? srows / 2 : nte) : srows);
+  *gpe = nte ? tile_grid(nte, stats, srows - *gp) : 0;
+  return !nte || *gpe > 0;
+}
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void gbl_void;

@@ -836,11 +836,7 @@ static void grid_1w(const ConvGeom& g, double* stats, int srows, int* tiles_h, i
   *tiles_h = (g.P + 3) / 4;
   *tiles_w = (g.Q + 63) / 64;
   *nt = (long long)g.N * *tiles_h * *tiles_w;
-  int n = 256;
-  if (n > *nt) n = (int)*nt;
-  if (n >= 64) n &= ~7;
-  if (stats && n > srows) n = srows;  // one statistics slab row per workgroup
-  *gp = n;
+  *gp = tile_grid(*nt, stats != nullptr, srows);
 }
 
 int launch_pool1w(const ConvGeom& g, const void* x, const void* wp, const float* bias, void* y, double* stats,
@@ -880,17 +876,8 @@ int launch_plain1w(const ConvGeom& g, const void* x, const void* wp, const float
   const int the = (g.P + 15) / 16, twe = (rem + 15) / 16;
   const long long nte = rem ? (long long)g.N * the * twe : 0;
   if (nt >= (1ll << 31) || nte >= (1ll << 31)) return ACFE_E_INVAL;
-  auto grid_for = [&](long long n, int rows_left) {
-    int gp = 256;
-    if (gp > n) gp = (int)n;
-    if (gp >= 64) gp &= ~7;
-    if (stats && gp > rows_left) gp = rows_left;  // one statistics slab row per workgroup
-    return gp;
-  };
-  // (small slabs: leave the second launch up to half of the rows)
-  const int gp = grid_for(nt, nte && stats ? srows - (int)(srows / 2 < nte ? srows / 2 : nte) : srows);
-  const int gpe = nte ? grid_for(nte, srows - gp) : 0;
-  if (nte && gpe <= 0) return ACFE_E_INVAL;
+  int gp, gpe;
+  if (!tile_grid_pair(nt, nte, stats != nullptr, srows, &gp, &gpe)) return ACFE_E_INVAL;
 #define P1W_L(PM_, D, S_, PRO_)                                                                                  \
   do {                                                                                                          \
     hipLaunchKernelGGL((k_conv3x3_1w<PM_, 2, D, S_, PRO_, 64>), dim3(gp), dim3(256), 0, s, g, (const uint16_t*)x, \
@@ -938,16 +925,8 @@ int launch_dgradbn1w(const ConvGeom& g, const void* dy, const void* wflip, void*
   const int the = (g.P + 15) / 16, twe = (rem + 15) / 16;
   const long long nte = rem ? (long long)g.N * the * twe : 0;
   if (nt >= (1ll << 31) || nte >= (1ll << 31)) return ACFE_E_INVAL;
-  auto grid_for = [&](long long n, int rows_left) {
-    int gp = 256;
-    if (gp > n) gp = (int)n;
-    if (gp >= 64) gp &= ~7;
-    if (gp > rows_left) gp = rows_left;
-    return gp;
-  };
-  const int gp = grid_for(nt, nte ? srows - (int)(srows / 2 < nte ? srows / 2 : nte) : srows);
-  const int gpe = nte ? grid_for(nte, srows - gp) : 0;
-  if (gp <= 0 || (nte && gpe <= 0)) return ACFE_E_INVAL;
+  int gp, gpe;  // (the BN sums' slab is always there)
+  if (!tile_grid_pair(nt, nte, true, srows, &gp, &gpe) || gp <= 0) return ACFE_E_INVAL;
   hipLaunchKernelGGL((k_conv3x3_1w<5, 2, false, true, false, 64>), dim3(gp), dim3(256), 0, s, g, (const uint16_t*)dy,
                      (const uint16_t*)wflip, nullptr, (uint16_t*)dx, part, th, tw, (int)nt, srows, nullptr, 0, 0);
   if (nte)

@@ -614,17 +614,7 @@ bool r64_grid(const ConvGeom& g, bool stats, int srows, R64Grid* o) {
   const int tiles_he = (g.P + 31) / 32, tiles_we = (rem + 15) / 16;
   const long long nte = rem ? (long long)g.N * tiles_he * tiles_we : 0;
   if (nt >= (1ll << 31) || nte >= (1ll << 31)) return false;
-  auto grid_for = [&](long long n, int rows_left) {
-    int gp = 256;
-    if (gp > n) gp = (int)n;
-    if (gp >= 64) gp &= ~7;
-    if (stats && gp > rows_left) gp = rows_left;  // one statistics slab row per workgroup
-    return gp;
-  };
-  // (small slabs: leave the second launch up to half of the rows)
-  const int gp = grid_for(nt, nte && stats ? srows - (int)(srows / 2 < nte ? srows / 2 : nte) : srows);
-  const int gpe = nte ? grid_for(nte, srows - gp) : 0;
-  if (nte && gpe <= 0) return false;
+  if (!tile_grid_pair(nt, nte, stats, srows, &o->gp, &o->gpe)) return false;
   o->rem = rem;
   o->tiles_h = tiles_h;
   o->tiles_w = tiles_w;
@@ -632,8 +622,6 @@ bool r64_grid(const ConvGeom& g, bool stats, int srows, R64Grid* o) {
   o->tiles_we = tiles_we;
   o->nt = nt;
   o->nte = nte;
-  o->gp = gp;
-  o->gpe = gpe;
   return true;
 }
 

@@ -214,6 +214,15 @@ def test_plain_k128_k256_remainder(env, cuda, C, K, want):
     _plain(env, cuda, N, H, W, C, K, f"plain c{C} k{K}")
 
 
+def test_plain_k32_odd_rows(env, cuda):
+    """K = 32 at an odd row count: one row per step (k_wgrad3x3_halo<32, false,
+    64, 1>; an even P takes the two-row kernel) on two chunks of C at 7 x 70,
+    the partial last 64-pixel column masked (K = 32 has no remainder kernel)."""
+    N, H, W, C, K = 3, 7, 70, 128, 32
+    _assert_plan(env[5], N, H, W, C, K, dict(nr=1, edge=0, qs=2, qse=0))
+    _plain(env, cuda, N, H, W, C, K, "plain c128 k32 odd rows")
+
+
 FORMS = ["drop-relu", "nodrop", "norelu", "add-f1", "add-f3"]
 
 
