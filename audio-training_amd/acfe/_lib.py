@@ -103,9 +103,6 @@ SIGNATURES: dict[str, list] = {
     "acfe_c1bn_stats": [P, I64, I32, P, I32, P, P, P, P, P],
     "acfe_c1bn_apply": [P, I64, I32, P, I32, P, P, P, I32, P, P],
     "acfe_c1bn_bwd": [P, P, I64, I32, P, I32, P, P, P, P, P, I32, F64, P, P, P, P, P, P, P, P],
-    "acfe_c1bn_stats_bn": [P, I64, I32, P, I32, P, P, P, P, P, P, I32, P],
-    "acfe_c1bn_apply_bn": [P, I64, I32, P, I32, P, P, P, I32, P, P, P, I32, P],
-    "acfe_c1bn_bwd_bn": [P, P, I64, I32, P, I32, P, P, P, P, P, I32, F64, P, P, P, P, P, P, P, P, P, I32, P],
     "acfe_channel_sum": [P, I64, I32, I32, P, P, F32, P],
     "acfe_add": [P, P, I64, I32, P, I32, P],
     "acfe_add_stats": [P, P, I64, I32, I32, P, I32, P, P],

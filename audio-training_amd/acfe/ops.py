@@ -28,11 +28,8 @@ UNPOOL = os.environ.get("ACFE_UNPOOL", "1") != "0"
 # ACFE_BN_PROLOGUE=0: every BatchNormalization writes its output in its own
 # apply pass instead of handing it to the consuming conv's input staging.
 PROLOGUE = os.environ.get("ACFE_BN_PROLOGUE", "1") != "0"
-# per-consumer switches of the prologue (A/B): the pooled 3x3 conv; the 1x1 + BN
-# node (off by default: its four streaming passes each redo the BN of x, which
-# measured 1 % slower per T1 step than the one apply pass it saves, r02ab)
+# per-consumer switch of the prologue (A/B): the pooled 3x3 conv
 PRO_POOL = os.environ.get("ACFE_BN_PROLOGUE_POOL", "1") != "0"
-PRO_C1 = os.environ.get("ACFE_BN_PROLOGUE_C1", "0") != "0"
 # ACFE_BN_PROLOGUE_1W=0: no BN prologue on the K = C = 128 one-wave conv (A/B)
 PRO_1W = os.environ.get("ACFE_BN_PROLOGUE_1W", "1") != "0"
 # ACFE_BN_REDUCE_FUSE=0: the BatchNormalization backward reduce runs as its own
@@ -63,6 +60,22 @@ def same_padding(n: int, k: int, s: int) -> tuple[int, int]:
 
 def valid_out(n: int, k: int, s: int) -> int:
     return (n - k) // s + 1
+
+
+def _conv_geometry(H, W, R, S, stride, padding) -> tuple[int, int, int, int]:
+    """(P, Q, pt, pl) of a Keras Conv2D: output size, top and left padding."""
+    if padding == "same":
+        P, pt = same_padding(H, R, stride)
+        Q, pl = same_padding(W, S, stride)
+        return P, Q, pt, pl
+    if padding == "valid":
+        return valid_out(H, R, stride), valid_out(W, S, stride), 0, 0
+    raise ValueError(padding)
+
+
+def _drop_args(drop) -> tuple[float, int]:
+    """(rate, seed) a kernel takes for the Dropout `drop` = (rate, seed) or None; rate 0 is no dropout."""
+    return drop if drop is not None and drop[0] > 0.0 else (0.0, 0)
 
 
 def _empty(shape, dtype, device):
@@ -144,6 +157,12 @@ def _no_stats(dev):
     return torch.empty(0, dtype=F64, device=dev)
 
 
+def _stats_slab(want, rows, ld, dev):
+    """The fp64 [rows][2][ld] slab a kernel writes its BN statistics partials
+    to; not wanted: the empty tensor, whose ptr() is NULL ("no statistics")."""
+    return _empty((rows, 2, ld), F64, dev) if want else _no_stats(dev)
+
+
 # Live kernel timing for bench.py: weight data_ptr -> list of (kind, ev0, ev1).
 # Events are recorded on the current torch stream, the stream every acfe
 # kernel is launched on.
@@ -206,18 +225,15 @@ def _conv_fwd(x, w, b, stride, pt, pl, P, Q, want_stats, drop=None, keep=None):
     dt = dtype_code(x.dtype)
     wp = pack_weights(w, x.dtype, False)
     y = _empty((N, P, Q, K), x.dtype, x.device)
-    stats = _no_stats(x.device)
-    if want_stats:
-        rows = lib.acfe_conv2d_stats_rows(N * P * Q, K)
-        stats = _empty((rows, 2, wp.shape[0]), F64, x.device)
-    args = (ptr(x), N, H, W, C, ptr(wp), K, R, S, stride, pt, pl, P, Q, ptr(b), ptr(y), dt,
-            ptr(stats) if want_stats else None)
+    stats = _stats_slab(want_stats, lib.acfe_conv2d_stats_rows(N * P * Q, K), wp.shape[0], x.device)
+    args = (ptr(x), N, H, W, C, ptr(wp), K, R, S, stride, pt, pl, P, Q, ptr(b), ptr(y), dt, ptr(stats))
+    rate, seed = _drop_args(drop)
     with _Timed(w, "fwd"):
         if keep is not None:
             call("acfe_conv2d_fwd_dropout_keep", ptr(x), N, H, W, C, ptr(wp), K, pt, pl, ptr(b), ptr(y), ptr(stats),
-                 float(drop[0]), int(drop[1]), ptr(keep), stream())
-        elif drop is not None and drop[0] > 0.0:
-            call("acfe_conv2d_fwd_dropout", *args, float(drop[0]), int(drop[1]), stream())
+                 float(rate), int(seed), ptr(keep), stream())
+        elif rate > 0.0:
+            call("acfe_conv2d_fwd_dropout", *args, float(rate), int(seed), stream())
         else:
             call("acfe_conv2d_fwd", *args, stream())
     return y, stats
@@ -233,6 +249,25 @@ def direct_grad(p):
     if g is None or g.dtype != F32 or not g.is_contiguous() or g.shape != p.shape:
         return None
     return g
+
+
+def _grad_into(p):
+    """(buffer, beta) for the kernel that forms the gradient of parameter p.
+    Arena parameters: the kernel accumulates straight into the flat gradient
+    buffer (beta 1) -- no separate add kernel per parameter; else a fresh
+    buffer (beta 0).  _grad_out finishes it."""
+    tgt = direct_grad(p)
+    return (tgt, 1.0) if tgt is not None else (_empty(p.shape, F32, p.device), 0.0)
+
+
+def _grad_out(p, buf, beta):
+    """What autograd gets for p once the kernel filling _grad_into's buffer is
+    enqueued: the buffer, or None for a gradient accumulated in the arena
+    (reported to grads_ready)."""
+    if beta == 0.0:
+        return buf
+    grads_ready(p)
+    return None
 
 
 # Data-parallel overlap (acfe.dp.GradBuckets.ready): called with each arena
@@ -296,25 +331,17 @@ def _conv_bwd(x, w, dy, stride, pt, pl, P, Q, need_dx, need_dw, need_db, bias=No
                 call("acfe_conv2d_dgrad", ptr(dy), N, P, Q, K, ptr(wf), C, R, S, stride, pt, pl, H, W, ptr(dx), dt,
                      ptr(ws), s)
     if need_dw:
-        # arena parameters: the split-K combine accumulates straight into the
-        # flat gradient buffer (beta 1) and autograd gets None -- no separate
-        # add kernel per weight
-        tgt = direct_grad(w)
-        dw = tgt if tgt is not None else _empty(w.shape, F32, w.device)
+        # (arena parameters: the split-K combine accumulates into the flat
+        # gradient buffer and autograd gets None)
+        dwt, beta = _grad_into(w)
         nws = lib.acfe_conv2d_wgrad_workspace(N, H, W, C, K, R, S, P, Q)
         ws = _empty((nws,), F32, x.device)
         with _Timed(w, "wgrad"):
-            call("acfe_conv2d_wgrad", ptr(x), N, H, W, C, ptr(dy), K, R, S, stride, pt, pl, P, Q, ptr(dw),
-                 1.0 if tgt is not None else 0.0, dt, ptr(ws), s)
-        if tgt is not None:
-            dw = None
-            grads_ready(w)
+            call("acfe_conv2d_wgrad", ptr(x), N, H, W, C, ptr(dy), K, R, S, stride, pt, pl, P, Q, ptr(dwt), beta, dt,
+                 ptr(ws), s)
+        dw = _grad_out(w, dwt, beta)
     if need_db:
-        tb = direct_grad(bias) if bias is not None else None
-        db = channel_sum(dy, K, into=tb)
-        if tb is not None:
-            db = None
-            grads_ready(bias)
+        db = _bias_grad(dy, K, bias) if bias is not None else channel_sum(dy, K)
     return dx, dw, db
 
 
@@ -388,11 +415,13 @@ def _attach_sum(t: torch.Tensor, part: torch.Tensor, rows: int, nrows: int | Non
     _tag(t, "_acfe_chpart", (part, lib.acfe_reduce_blocks(rows) if nrows is None else nrows))
 
 
-def channel_sum(x: torch.Tensor, C: int, into: torch.Tensor | None = None) -> torch.Tensor:
-    """Per-channel sum of x [..., C] in fp32; with `into` (an arena gradient
-    view) it is accumulated there instead (beta 1)."""
+def channel_sum(x: torch.Tensor, C: int, into: torch.Tensor | None = None, beta: float = 1.0) -> torch.Tensor:
+    """Per-channel sum of x [..., C] in fp32 -> a fresh [C] tensor, or with
+    `into`: into = beta * into + sum (an arena gradient view with beta 1, or a
+    buffer of _grad_into with its beta).  Where x carries its channel-sum slab
+    (_attach_sum) only the slab is finalized; else x is read."""
     out = into if into is not None else _empty((C,), F32, x.device)
-    beta = 1.0 if into is not None else 0.0
+    beta = beta if into is not None else 0.0
     lazy = _tagged(x, "_acfe_chpart")
     if lazy is not None and lazy[0].shape[-1] == C:
         part, nrows = lazy
@@ -404,6 +433,13 @@ def channel_sum(x: torch.Tensor, C: int, into: torch.Tensor | None = None) -> to
     return out
 
 
+def _bias_grad(g, K, bias):
+    """The gradient of `bias` [K] for autograd: the channel sums of the conv output gradient g."""
+    db, beta = _grad_into(bias)
+    channel_sum(g, K, into=db, beta=beta)
+    return _grad_out(bias, db, beta)
+
+
 def conv2d(x, w, b=None, stride=1, padding="same", want_stats=False, link=None):
     """Keras Conv2D on NHWC x with KRSC weights. Returns (y, stats_partial).
     link: a ResidualLink of the BatchNormalization that also reads x (a
@@ -413,13 +449,7 @@ def conv2d(x, w, b=None, stride=1, padding="same", want_stats=False, link=None):
     the conv must then be created after the BN (its backward runs first)."""
     N, H, W, C = x.shape
     K, R, S, _ = w.shape
-    if padding == "same":
-        P, pt = same_padding(H, R, stride)
-        Q, pl = same_padding(W, S, stride)
-    elif padding == "valid":
-        P, Q, pt, pl = valid_out(H, R, stride), valid_out(W, S, stride), 0, 0
-    else:
-        raise ValueError(padding)
+    P, Q, pt, pl = _conv_geometry(H, W, R, S, stride, padding)
     if link is not None and not (x.is_contiguous() and (P, Q) != (0, 0)):
         # the conv cannot hand dX over: autograd accumulates it instead, and
         # the linked BN must not wait for it (ResidualLink.declined)
@@ -429,21 +459,25 @@ def conv2d(x, w, b=None, stride=1, padding="same", want_stats=False, link=None):
 
 
 # ------------------------------------------------------------------ stem (folded C=1)
+def _stem_fwd(x, w, b, pt, pl, out_dtype, want_stats):
+    """acfe_stem_fwd -> (y, stats slab or empty, folded weights).
+    x: [N, H, W] (one folded channel); w: [16, R, S, Crep] fp32."""
+    N, H, W = x.shape
+    K, R, S, rep = w.shape
+    weff = _empty((R, S, K), F32, x.device)  # folded, RSK
+    s = stream()
+    call("acfe_stem_fold_weights", ptr(w), K, R, S, rep, ptr(weff), s)
+    y = _empty((N, H, W, K), out_dtype, x.device)
+    stats = _stats_slab(want_stats, lib.acfe_stem_blocks(N, H, W), K, x.device)
+    call("acfe_stem_fwd", ptr(x), dtype_code(x.dtype), N, H, W, R, S, pt, pl, ptr(weff), ptr(b), ptr(y),
+         dtype_code(out_dtype), ptr(stats), s)
+    return y, stats, weff
+
+
 class _StemFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, pt, pl, out_dtype, want_stats):
-        # x: [N, H, W] (one folded channel); w: [16, R, S, Crep] fp32
-        N, H, W = x.shape
-        K, R, S, rep = w.shape
-        weff = _empty((R, S, K), F32, x.device)  # folded, RSK
-        s = stream()
-        call("acfe_stem_fold_weights", ptr(w), K, R, S, rep, ptr(weff), s)
-        y = _empty((N, H, W, K), out_dtype, x.device)
-        stats = _no_stats(x.device)
-        if want_stats:
-            stats = _empty((lib.acfe_stem_blocks(N, H, W), 2, K), F64, x.device)
-        call("acfe_stem_fwd", ptr(x), dtype_code(x.dtype), N, H, W, R, S, pt, pl, ptr(weff), ptr(b), ptr(y),
-             dtype_code(out_dtype), ptr(stats) if want_stats else None, s)
+        y, stats, weff = _stem_fwd(x, w, b, pt, pl, out_dtype, want_stats)
         ctx.save_for_backward(x, w, weff)
         ctx.conf = (pt, pl, b is not None)
         ctx.mark_non_differentiable(stats)
@@ -483,25 +517,9 @@ class _StemBNPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, gamma, beta, mmean, mvar, conf):
         pt, pl, out_dtype, kh, kw, relu, eps, momentum, want_stats = conf
-        N, H, W = x.shape
-        K, R, S, rep = w.shape
-        dev = x.device
-        s = stream()
-        weff = _empty((R, S, K), F32, dev)
-        call("acfe_stem_fold_weights", ptr(w), K, R, S, rep, ptr(weff), s)
-        y = _empty((N, H, W, K), out_dtype, dev)
-        st = _empty((lib.acfe_stem_blocks(N, H, W), 2, K), F64, dev)
-        call("acfe_stem_fwd", ptr(x), dtype_code(x.dtype), N, H, W, R, S, pt, pl, ptr(weff), ptr(b), ptr(y),
-             dtype_code(out_dtype), ptr(st), s)
+        y, st, weff = _stem_fwd(x, w, b, pt, pl, out_dtype, True)
         _, saved = _bn_fwd(y, gamma, beta, st, mmean, mvar, True, relu, eps, momentum, None)
-        P, Q = H // kh, W // kw
-        yp = _empty((N, P, Q, K), y.dtype, dev)
-        amax = _empty((N, P, Q, K), torch.uint8, dev)
-        pst = _no_stats(dev)
-        if want_stats:
-            pst = _empty((lib.acfe_reduce_blocks(N * P * Q), 2, K), F64, dev)
-        call("acfe_bn_maxpool2d_fused", ptr(y), N, H, W, K, ptr(saved[0]), ptr(saved[1]), int(relu), kh, kw, ptr(yp),
-             ptr(amax), ptr(pst) if want_stats else None, dtype_code(y.dtype), s)
+        yp, amax, pst = _bn_pool_fwd(y, saved, relu, kh, kw, want_stats)
         ctx.save_for_backward(x, w, weff, y, amax, *saved)
         ctx.conf, ctx.gb = conf, (gamma, beta)
         ctx.mark_non_differentiable(pst)
@@ -515,15 +533,9 @@ class _StemBNPoolFn(torch.autograd.Function):
         _, R, S, rep = w.shape
         dev = y.device
         s = stream()
-        scale, shift, mean, invstd = saved
-        g = g.contiguous()
-        gu = _empty(y.shape, g.dtype, dev)
-        rows = N * H * W
-        nrows = lib.acfe_reduce_blocks(rows)
-        part = _empty((nrows * 2 * K,), F64, dev)
-        call("acfe_maxpool2d_bwd_argmax_bn", ptr(amax), ptr(g), N, H, W, K, kh, kw, ptr(gu), dtype_code(g.dtype),
-             ptr(y), ptr(scale), ptr(shift), ptr(mean), ptr(invstd), int(relu), ptr(part), s)
-        coef, dgamma, dbeta = _bn_bwd_coef(part, nrows, K, rows, saved, True, ctx.gb, dev)
+        scale, shift = saved[:2]
+        gu, part = _pool_bwd_bn(y, amax, g, kh, kw, saved, relu)
+        gu, coef, dgamma, dbeta = _bn_bwd_head(y, gu, saved, relu, True, ctx.gb, part)
         nb = lib.acfe_stem_blocks(N, H, W)
         dx = _empty(x.shape, x.dtype, dev)
         dw = _empty(w.shape, F32, dev)
@@ -551,10 +563,7 @@ def stem_bn_max_pool(x, w, b, out_dtype, gamma, beta, mmean, mvar, kh, kw, relu=
                      want_stats=False):
     """MaxPool2D((kh, kw))(BatchNormalization(stem_conv(x, w, b))) in training
     (stem_bn_pool_ok) -> (y, stats slab of y or None)."""
-    N, H, W = x.shape
-    _, R, S, _ = w.shape
-    _, pt = same_padding(H, R, 1)
-    _, pl = same_padding(W, S, 1)
+    _, _, pt, pl = _conv_geometry(x.shape[1], x.shape[2], w.shape[1], w.shape[2], 1, "same")
     conf = (pt, pl, out_dtype, kh, kw, bool(relu), float(eps), float(momentum), bool(want_stats))
     y, st = _StemBNPoolFn.apply(x, w, b, gamma, beta, mmean, mvar, conf)
     return y, (st if want_stats else None)
@@ -562,10 +571,7 @@ def stem_bn_max_pool(x, w, b, out_dtype, gamma, beta, mmean, mvar, kh, kw, relu=
 
 def stem_conv(x, w, b, out_dtype, want_stats=False):
     """'same' stride-1 conv of a one-channel map x [N,H,W] whose Cin copies are folded."""
-    N, H, W = x.shape
-    _, R, S, _ = w.shape
-    _, pt = same_padding(H, R, 1)
-    _, pl = same_padding(W, S, 1)
+    _, _, pt, pl = _conv_geometry(x.shape[1], x.shape[2], w.shape[1], w.shape[2], 1, "same")
     return _StemFn.apply(x, w, b, pt, pl, out_dtype, want_stats)
 
 
@@ -603,6 +609,21 @@ class ResidualLink:
         return p
 
 
+def _bn_finalize(part, nrows, ld, C, rows, gamma, beta, mmean, mvar, training, eps, momentum, dev):
+    """acfe_bn_finalize -> (scale, shift, mean, invstd) of C channels.  Training:
+    from the statistics slab `part` (nrows rows of leading dimension ld, over
+    `rows` values per channel), the moving statistics updated; else from the
+    moving statistics."""
+    scale, shift, mean, invstd = (_empty((C,), F32, dev) for _ in range(4))
+    if training:
+        call("acfe_bn_finalize", ptr(part), nrows, ld, C, float(rows), ptr(gamma), ptr(beta), eps, momentum,
+             ptr(mmean), ptr(mvar), 1, ptr(scale), ptr(shift), ptr(mean), ptr(invstd), stream())
+    else:
+        call("acfe_bn_finalize", None, 0, C, C, 0.0, ptr(gamma), ptr(beta), eps, momentum, ptr(mmean), ptr(mvar),
+             0, ptr(scale), ptr(shift), ptr(mean), ptr(invstd), stream())
+    return scale, shift, mean, invstd
+
+
 def _bn_fwd(x, gamma, beta, stats, mmean, mvar, training, relu, eps, momentum, out_dtype, defer=False, grad=False):
     """Batch statistics (given slab or acfe_bn_stats) -> finalize -> apply. Returns (y, saved).
     grad: a backward can run (the node's ctx.needs_input_grad); only then is y
@@ -615,22 +636,16 @@ def _bn_fwd(x, gamma, beta, stats, mmean, mvar, training, relu, eps, momentum, o
     dt = dtype_code(x.dtype)
     dev = x.device
     s = stream()
-    scale, shift, mean, invstd = (_empty((C,), F32, dev) for _ in range(4))
-    if training:
-        if stats is None or stats.numel() == 0:
-            nrows = lib.acfe_reduce_blocks(rows)
-            part = _empty((nrows * 2 * C,), F64, dev)
-            call("acfe_bn_stats", ptr(x), rows, C, dt, ptr(part), s)
-            ld = C
-        else:
-            part = stats
-            ld = stats.shape[-1]
-            nrows = stats.numel() // (2 * ld)
-        call("acfe_bn_finalize", ptr(part), nrows, ld, C, float(rows), ptr(gamma), ptr(beta), eps, momentum,
-             ptr(mmean), ptr(mvar), 1, ptr(scale), ptr(shift), ptr(mean), ptr(invstd), s)
-    else:
-        call("acfe_bn_finalize", None, 0, C, C, 0.0, ptr(gamma), ptr(beta), eps, momentum, ptr(mmean), ptr(mvar),
-             0, ptr(scale), ptr(shift), ptr(mean), ptr(invstd), s)
+    part, nrows, ld = stats, 0, C  # (eval mode: no slab is read)
+    if training and (stats is None or stats.numel() == 0):
+        nrows = lib.acfe_reduce_blocks(rows)
+        part = _empty((nrows * 2 * C,), F64, dev)
+        call("acfe_bn_stats", ptr(x), rows, C, dt, ptr(part), s)
+    elif training:
+        ld = stats.shape[-1]
+        nrows = stats.numel() // (2 * ld)
+    scale, shift, mean, invstd = _bn_finalize(part, nrows, ld, C, rows, gamma, beta, mmean, mvar, training, eps,
+                                              momentum, dev)
     if out_dtype is None:  # affine only: the caller applies it (bn_max_pool)
         return None, (scale, shift, mean, invstd)
     y = _empty(x.shape, out_dtype, dev)
@@ -690,19 +705,16 @@ def _conv_fwd_bn(xb, w, b, want_stats, drop, keep=None):
     x, scale, shift, relu = _prologue_args(xb)
     wp = pack_weights(w, xb.dtype, False)
     y = _empty((N, H, W, K), xb.dtype, xb.device)
-    stats = _no_stats(xb.device)
-    if want_stats:
-        stats = _empty((lib.acfe_conv2d_stats_rows(N * H * W, K), 2, wp.shape[0]), F64, xb.device)
-    rate, seed = drop if drop is not None and drop[0] > 0.0 else (0.0, 0)
+    stats = _stats_slab(want_stats, lib.acfe_conv2d_stats_rows(N * H * W, K), wp.shape[0], xb.device)
+    rate, seed = _drop_args(drop)
     with _Timed(w, "fwd"):
         if keep is not None:
             call("acfe_conv2d_fwd_bn_keep", ptr(x), N, H, W, C, ptr(wp), K, 1, 1, ptr(b), ptr(y), ptr(stats),
                  float(rate), int(seed), ptr(scale), ptr(shift), int(relu), ptr(xb), ptr(keep), dtype_code(xb.dtype),
                  stream())
         else:
-            call("acfe_conv2d_fwd_bn", ptr(x), N, H, W, C, ptr(wp), K, 1, 1, ptr(b), ptr(y),
-                 ptr(stats) if want_stats else None, float(rate), int(seed), ptr(scale), ptr(shift), int(relu),
-                 ptr(xb), dtype_code(xb.dtype), stream())
+            call("acfe_conv2d_fwd_bn", ptr(x), N, H, W, C, ptr(wp), K, 1, 1, ptr(b), ptr(y), ptr(stats),
+                 float(rate), int(seed), ptr(scale), ptr(shift), int(relu), ptr(xb), dtype_code(xb.dtype), stream())
     return y, stats
 
 
@@ -738,65 +750,77 @@ def _bn_bwd(x, dy, saved, relu, training, add=None, drop=None, mask_in=False, po
     that produced dy (acfe_maxpool2d_bwd_argmax_bn): no reduce pass; the same
     when dy carries the slab of the dgrad that produced it (acfe_conv2d_dgrad_bn,
     tagged _acfe_bnpart for this x)."""
+    dy, coef, dgamma, dbeta = _bn_bwd_head(x, dy, saved, relu, training, params, part)
+    dx = _empty(x.shape, x.dtype, x.device)
+    _bn_bwd_apply(dx, dy, x, saved[0], saved[1], int(relu) | (2 if mask_in else 0), coef, _residual(add, x), drop,
+                  pool, sub)
+    return dx, dgamma, dbeta
+
+
+def _bn_bwd_head(x, dy, saved, relu, training, params, part=None):
+    """The BN backward of input x up to its coefficients -> (dy contiguous, coef,
+    dgamma, dbeta): the reduce slab is `part`, or the one dy carries from the
+    dgrad that produced it (_acfe_bnpart, tagged for this x), or comes from
+    the reduce pass (acfe_bn_bwd_reduce); then _bn_bwd_coef."""
     scale, shift, mean, invstd = saved
     C = x.shape[-1]
     rows = x.numel() // C
-    dev = x.device
-    s = stream()
-    nrows = lib.acfe_reduce_blocks(rows)
-    prow = nrows
+    prow = nrows = lib.acfe_reduce_blocks(rows)
     if part is None:
+        # (looked up before .contiguous(): the tag lives on the tensor object autograd delivered)
         lazy = _tagged(dy, "_acfe_bnpart")
         if lazy is not None and lazy[2] == (x.data_ptr(), tuple(x.shape), bool(relu)):
             part, prow = lazy[0], lazy[1]
     dy = dy.contiguous()
     if part is None:
-        part = _empty((nrows * 2 * C,), F64, dev)
+        part = _empty((nrows * 2 * C,), F64, x.device)
         call("acfe_bn_bwd_reduce", ptr(dy), dtype_code(dy.dtype), ptr(x), dtype_code(x.dtype), rows, C, ptr(scale),
-             ptr(shift), ptr(mean), ptr(invstd), int(relu), ptr(part), s)
-    coef, dgamma, dbeta = _bn_bwd_coef(part, prow, C, rows, saved, training, params, dev)
-    dx = _empty(x.shape, x.dtype, dev)
-    rate, seed = drop if drop is not None and drop[0] > 0.0 else (0.0, 0)
-    if add is not None:
-        assert rate == 0.0
-        add = add.contiguous()
-        assert add.dtype == x.dtype and add.shape == x.shape
+             ptr(shift), ptr(mean), ptr(invstd), int(relu), ptr(part), stream())
+    return (dy, *_bn_bwd_coef(part, prow, C, rows, saved, training, params, x.device))
+
+
+def _residual(add, x):
+    """The gradient `add` a BN backward apply sums into the gradient of x (or None)."""
+    if add is None:
+        return None
+    assert add.dtype == x.dtype and add.shape == x.shape
+    return add.contiguous()
+
+
+def _bn_bwd_apply(dx, dy, x, scale, shift, flags, coef, add=None, drop=None, pool=None, sub=None):
+    """The BN backward apply pass: writes dx (the gradient of the BN input x)
+    from dy and the coefficients of _bn_bwd_head; flags: 1 = the BN's ReLU,
+    2 = x is a ReLU output whose mask [x > 0] is applied too (dx is tagged
+    _acfe_relu_masked).  At most one of: add (summed into dx), drop (dx
+    passed back through that Dropout), pool = (gradient, k) of a shortcut
+    AveragePooling2D(x) folded in, sub = (dX, k) of a 1x1 stride-k conv
+    shortcut, nonzero at the pixels (k p, k q) only."""
+    C = x.shape[-1]
+    rows = x.numel() // C
+    rate, seed = _drop_args(drop)
+    assert sum((add is not None, rate > 0.0, pool is not None, sub is not None)) <= 1
     # per-channel sums of dx ride along (bias gradient of the conv producing x)
     want_sum = FUSE and _sums_ok(dx) and _sums_ok(dy) and _sums_ok(x) and (add is None or _sums_ok(add))
-    sums = _empty((nrows, 2, C), F64, dev) if want_sum else None
-    flags = int(relu) | (2 if mask_in else 0)
-    if sub is not None:  # 1x1 stride-k shortcut's dX (pixels (k p, k q) only) folded in
-        gs, k = sub
+    sums = _empty((lib.acfe_reduce_blocks(rows), 2, C), F64, x.device) if want_sum else None
+    dyt, xt, s = dtype_code(dy.dtype), dtype_code(x.dtype), stream()
+    if sub is not None or pool is not None:  # a shortcut's gradient gs folded in
+        N, H, W, _ = x.shape
+        gs, k = sub if sub is not None else pool
         gs = gs.contiguous()
-        assert rate == 0.0 and add is None and pool is None and gs.dtype == x.dtype
-        N, H, W, _ = x.shape
-        call("acfe_bn_bwd_apply_sub", ptr(dy), dtype_code(dy.dtype), ptr(x), dtype_code(x.dtype), N, H, W, C,
-             ptr(scale), ptr(shift), flags, ptr(coef), ptr(gs), int(k), ptr(dx), dtype_code(x.dtype), ptr(sums), s)
-        if want_sum:
-            _attach_sum(dx, sums, rows)
-        if mask_in:
-            _tag(dx, "_acfe_relu_masked", True)
-        return dx, dgamma, dbeta
-    if pool is not None:  # shortcut AveragePooling2D(x) backward folded in
-        gp, k = pool
-        gp = gp.contiguous()
-        assert rate == 0.0 and add is None and gp.dtype == x.dtype
-        N, H, W, _ = x.shape
-        call("acfe_bn_bwd_apply_pool", ptr(dy), dtype_code(dy.dtype), ptr(x), dtype_code(x.dtype), N, H, W, C,
-             ptr(scale), ptr(shift), flags, ptr(coef), ptr(gp), int(k), ptr(dx), dtype_code(x.dtype), ptr(sums), s)
-        if want_sum:
-            _attach_sum(dx, sums, rows)
-        if mask_in:
-            _tag(dx, "_acfe_relu_masked", True)
-        return dx, dgamma, dbeta
-    call("acfe_bn_bwd_apply_ex", ptr(dy), dtype_code(dy.dtype), ptr(x), dtype_code(x.dtype), rows, C, ptr(scale),
-         ptr(shift), flags, ptr(coef), ptr(add), float(rate), int(seed), ptr(dx), dtype_code(x.dtype), ptr(sums),
-         s)
+        assert gs.dtype == x.dtype
+        if sub is not None:
+            call("acfe_bn_bwd_apply_sub", ptr(dy), dyt, ptr(x), xt, N, H, W, C, ptr(scale), ptr(shift), flags,
+                 ptr(coef), ptr(gs), int(k), ptr(dx), xt, ptr(sums), s)
+        else:
+            call("acfe_bn_bwd_apply_pool", ptr(dy), dyt, ptr(x), xt, N, H, W, C, ptr(scale), ptr(shift), flags,
+                 ptr(coef), ptr(gs), int(k), ptr(dx), xt, ptr(sums), s)
+    else:
+        call("acfe_bn_bwd_apply_ex", ptr(dy), dyt, ptr(x), xt, rows, C, ptr(scale), ptr(shift), flags, ptr(coef),
+             ptr(add), float(rate), int(seed), ptr(dx), xt, ptr(sums), s)
     if want_sum:
         _attach_sum(dx, sums, rows)
-    if mask_in:
+    if flags & 2:
         _tag(dx, "_acfe_relu_masked", True)
-    return dx, dgamma, dbeta
 
 
 class _BNFn(torch.autograd.Function):
@@ -840,28 +864,10 @@ def _bn_bwd_pending(x, dy, saved, relu, training, add, mask_in, params):
     """_bn_bwd up to its apply pass: the reduce (or the slab the producing
     dgrad formed) and the coefficients run now; dx comes back UNWRITTEN with
     the apply's arguments attached (_acfe_bwd_pending), for _take_pending."""
-    scale, shift, mean, invstd = saved
-    C = x.shape[-1]
-    rows = x.numel() // C
-    dev = x.device
-    nrows = lib.acfe_reduce_blocks(rows)
-    prow = nrows
-    part = None
-    lazy = _tagged(dy, "_acfe_bnpart")
-    if lazy is not None and lazy[2] == (x.data_ptr(), tuple(x.shape), bool(relu)):
-        part, prow = lazy[0], lazy[1]
-    dy = dy.contiguous()
-    if part is None:
-        part = _empty((nrows * 2 * C,), F64, dev)
-        call("acfe_bn_bwd_reduce", ptr(dy), dtype_code(dy.dtype), ptr(x), dtype_code(x.dtype), rows, C, ptr(scale),
-             ptr(shift), ptr(mean), ptr(invstd), int(relu), ptr(part), stream())
-    coef, dgamma, dbeta = _bn_bwd_coef(part, prow, C, rows, saved, training, params, dev)
-    if add is not None:
-        add = add.contiguous()
-        assert add.dtype == x.dtype and add.shape == x.shape
-    dx = _empty(x.shape, x.dtype, dev)
+    dy, coef, dgamma, dbeta = _bn_bwd_head(x, dy, saved, relu, training, params)
+    dx = _empty(x.shape, x.dtype, x.device)
     flags = int(relu) | (2 if mask_in else 0)
-    dx._acfe_bwd_pending = ((dy, x, scale, shift, flags, coef, add), dx._version)
+    dx._acfe_bwd_pending = ((dy, x, saved[0], saved[1], flags, coef, _residual(add, x)), dx._version)
     return dx, dgamma, dbeta
 
 
@@ -877,22 +883,6 @@ def _take_pending(g):
     if g._version != ver:
         raise RuntimeError("pending BatchNormalization gradient was modified before its apply ran")
     return args
-
-
-def _apply_pending(g, args):
-    """Write the pending gradient g with the apply pass (acfe_bn_bwd_apply_ex),
-    its channel sums attached as _bn_bwd does."""
-    dy, x, scale, shift, flags, coef, add = args
-    C = x.shape[-1]
-    rows = x.numel() // C
-    want_sum = FUSE and _sums_ok(g) and _sums_ok(dy) and _sums_ok(x) and (add is None or _sums_ok(add))
-    sums = _empty((lib.acfe_reduce_blocks(rows), 2, C), F64, x.device) if want_sum else None
-    call("acfe_bn_bwd_apply_ex", ptr(dy), dtype_code(dy.dtype), ptr(x), dtype_code(x.dtype), rows, C, ptr(scale),
-         ptr(shift), flags, ptr(coef), ptr(add), 0.0, 0, ptr(g), dtype_code(x.dtype), ptr(sums), stream())
-    if want_sum:
-        _attach_sum(g, sums, rows)
-    if flags & 2:
-        _tag(g, "_acfe_relu_masked", True)
 
 
 def batch_norm(x, gamma, beta, mmean, mvar, training, relu=False, stats=None, eps=1e-3, momentum=0.99, link=None,
@@ -965,39 +955,26 @@ def _wgrad_bnbwd(x, w, g, pend, need_db, bias, rate=0.0, seed=0, keep=None):
     dev = x.device
     s = stream()
     dy, u, scale, shift, flags, coef, add = pend
-    tgt = direct_grad(w)
-    dwt = tgt if tgt is not None else _empty(w.shape, F32, dev)
+    dwt, beta = _grad_into(w)
     ws = _empty((lib.acfe_conv2d_wgrad_workspace(N, H, W, C, K, 3, 3, H, W),), F32, dev)
     srows = lib.acfe_conv2d_wgrad_bnbwd_rows(N, H, W, C, K)
     sums = _empty((srows, 2, K), F64, dev)
     with _Timed(w, "wgrad"):
         if keep is not None and add is None and rate > 0.0:
             call("acfe_conv2d_wgrad_bnbwd_keep", ptr(x), N, H, W, C, ptr(dy), ptr(u), K, ptr(scale), ptr(shift),
-                 int(flags), ptr(coef), float(rate), int(seed), ptr(keep), ptr(g), ptr(dwt),
-                 1.0 if tgt is not None else 0.0, ptr(ws), ptr(sums), s)
+                 int(flags), ptr(coef), float(rate), int(seed), ptr(keep), ptr(g), ptr(dwt), beta, ptr(ws),
+                 ptr(sums), s)
         else:
             call("acfe_conv2d_wgrad_bnbwd", ptr(x), N, H, W, C, ptr(dy), ptr(u), K, ptr(scale), ptr(shift),
-                 int(flags), ptr(coef), ptr(add), float(rate), int(seed), ptr(g), ptr(dwt),
-                 1.0 if tgt is not None else 0.0, ptr(ws), ptr(sums), s)
+                 int(flags), ptr(coef), ptr(add), float(rate), int(seed), ptr(g), ptr(dwt), beta, ptr(ws),
+                 ptr(sums), s)
     if flags & 2:
         _tag(g, "_acfe_relu_masked", True)
     # g's channel sums: the bias gradient here and of any other conv receiving
     # g (a conv shortcut's, through autograd: channel_sum)
     _attach_sum(g, sums, g.numel() // K, srows)
-    dw = dwt
-    if tgt is not None:
-        dw = None
-        grads_ready(w)
-    db = None
-    if need_db:
-        tb = direct_grad(bias)
-        out = tb if tb is not None else _empty((K,), F32, dev)
-        call("acfe_channel_sum_finalize", ptr(sums), srows, K, 1.0 if tb is not None else 0.0, ptr(out), s)
-        db = out
-        if tb is not None:
-            db = None
-            grads_ready(bias)
-    return dw, db
+    # (_bias_grad finalizes the slab just attached to g, acfe_channel_sum_finalize: it does not read g)
+    return _grad_out(w, dwt, beta), (_bias_grad(g, K, bias) if need_db else None)
 
 
 def _conv_bn_bwd_fold(ctx, x, w, u, dy, saved, relu, training):
@@ -1007,25 +984,10 @@ def _conv_bn_bwd_fold(ctx, x, w, u, dy, saved, relu, training):
     (written for the dgrad, its channel sums = the bias gradient) -- the apply
     pass over the tensor is gone.  Same values as _bn_bwd -> _conv_bwd."""
     N, H, W, C = x.shape
-    K = w.shape[0]
-    dev = x.device
-    s = stream()
-    scale, shift, mean, invstd = saved
-    rows = u.numel() // K
-    dy = dy.contiguous()
-    part = None
-    prow = nrows = lib.acfe_reduce_blocks(rows)
-    lazy = _tagged(dy, "_acfe_bnpart")
-    if lazy is not None and lazy[2] == (u.data_ptr(), tuple(u.shape), bool(relu)):
-        part, prow = lazy[0], lazy[1]
-    if part is None:
-        part = _empty((nrows * 2 * K,), F64, dev)
-        call("acfe_bn_bwd_reduce", ptr(dy), dtype_code(dy.dtype), ptr(u), dtype_code(u.dtype), rows, K, ptr(scale),
-             ptr(shift), ptr(mean), ptr(invstd), int(relu), ptr(part), s)
-    coef, dgamma, dbeta = _bn_bwd_coef(part, prow, K, rows, saved, training, ctx.gb, dev)
-    g = _empty(u.shape, u.dtype, dev)  # the conv output gradient
-    rate, seed = ctx.drop if ctx.drop is not None else (0.0, 0)
-    dw, db = _wgrad_bnbwd(x, w, g, (dy, u, scale, shift, int(relu), coef, None),
+    dy, coef, dgamma, dbeta = _bn_bwd_head(u, dy, saved, relu, training, ctx.gb)
+    g = _empty(u.shape, u.dtype, x.device)  # the conv output gradient
+    rate, seed = _drop_args(ctx.drop)
+    dw, db = _wgrad_bnbwd(x, w, g, (dy, u, saved[0], saved[1], int(relu), coef, None),
                           ctx.has_b and ctx.needs_input_grad[2], ctx.bias, rate, seed, getattr(ctx, "keep", None))
     dx = None
     if ctx.needs_input_grad[0]:
@@ -1041,13 +1003,7 @@ def conv_dropout_bn(x, w, b, gamma, beta, mmean, mvar, training, rate=0.0, seed=
         u, _ = conv2d(x, w, b, stride, padding)
         u = dropout(u, rate, training, seed)
         return batch_norm(u, gamma, beta, mmean, mvar, training, relu=relu, eps=eps, momentum=momentum)
-    N, H, W, C = x.shape
-    K, R, S, _ = w.shape
-    if padding == "same":
-        P, pt = same_padding(H, R, stride)
-        Q, pl = same_padding(W, S, stride)
-    else:
-        P, Q, pt, pl = valid_out(H, R, stride), valid_out(W, S, stride), 0, 0
+    P, Q, pt, pl = _conv_geometry(x.shape[1], x.shape[2], w.shape[1], w.shape[2], stride, padding)
     if training and rate > 0.0 and seed is None:
         seed = next_seed()
     conf = (stride, pt, pl, P, Q, float(rate), int(seed or 0), bool(training), bool(relu), float(eps),
@@ -1066,8 +1022,9 @@ class _C1BNFn(torch.autograd.Function):
     """BatchNormalization(+ReLU) of a 1x1 Conv2D with 16 input channels as one
     node (csrc/c1bn.hip): the conv output is never stored; its statistics come
     from the 16x16 Gram matrix of x, the backward's sums from g^T x.  A pending
-    BN output x (the block's bn2a0) is never written: every pass reads the BN
-    input and applies the BN (+ReLU) itself (acfe_c1bn_*_bn)."""
+    BN output x (the block's bn2a0) is written first: the node's four streaming
+    passes would each redo the BN of x, which measured slower than the one
+    apply pass it saves."""
 
     @staticmethod
     def forward(ctx, x, w, b, gamma, beta, mmean, mvar, conf):
@@ -1078,43 +1035,22 @@ class _C1BNFn(torch.autograd.Function):
         K = w.shape[0]
         M = N * H * W
         dev, s = x.device, stream()
-        pend = _pending(x)
-        if pend is not None and not (PRO_C1 and pend[0].is_contiguous() and pend[0].data_ptr() % 16 == 0
-                                     and pend[0].shape == x.shape):
-            materialize(x)
-            pend = None
-        # (x stays pending: a later reader would materialize it)
-        xr, xsc, xsh, xrelu = pend if pend is not None else (x, None, None, False)
-        scale, shift, mean, invstd = (_empty((K,), F32, dev) for _ in range(4))
+        materialize(x)
         ws = _empty((lib.acfe_c1bn_workspace(M, C, K),), F32, dev)
         gram = _empty((272,), F32, dev)
         part = _empty((1, 2, K), F64, dev)
-        if pend is not None:
-            call("acfe_c1bn_stats_bn", ptr(xr), M, C, ptr(w), K, ptr(b), ptr(part), ptr(gram), ptr(ws), ptr(xsc),
-                 ptr(xsh), int(xrelu), s)
-        else:
-            call("acfe_c1bn_stats", ptr(x), M, C, ptr(w), K, ptr(b), ptr(part), ptr(gram), ptr(ws), s)
-        if training:
-            call("acfe_bn_finalize", ptr(part), 1, K, K, float(M), ptr(gamma), ptr(beta), eps, momentum,
-                 ptr(mmean), ptr(mvar), 1, ptr(scale), ptr(shift), ptr(mean), ptr(invstd), s)
-        else:
-            call("acfe_bn_finalize", None, 0, K, K, 0.0, ptr(gamma), ptr(beta), eps, momentum, ptr(mmean),
-                 ptr(mvar), 0, ptr(scale), ptr(shift), ptr(mean), ptr(invstd), s)
+        call("acfe_c1bn_stats", ptr(x), M, C, ptr(w), K, ptr(b), ptr(part), ptr(gram), ptr(ws), s)
+        scale, shift, mean, invstd = _bn_finalize(part, 1, K, K, M, gamma, beta, mmean, mvar, training, eps, momentum,
+                                                  dev)
         y = _empty((N, H, W, K), x.dtype, dev)
-        if pend is not None:
-            call("acfe_c1bn_apply_bn", ptr(xr), M, C, ptr(w), K, ptr(b), ptr(scale), ptr(shift), int(relu), ptr(y),
-                 ptr(xsc), ptr(xsh), int(xrelu), s)
-            ctx.save_for_backward(xr, w, b, scale, shift, mean, invstd, gram, xsc, xsh)
-        else:
-            call("acfe_c1bn_apply", ptr(x), M, C, ptr(w), K, ptr(b), ptr(scale), ptr(shift), int(relu), ptr(y), s)
-            ctx.save_for_backward(x, w, b, scale, shift, mean, invstd, gram, None, None)
+        call("acfe_c1bn_apply", ptr(x), M, C, ptr(w), K, ptr(b), ptr(scale), ptr(shift), int(relu), ptr(y), s)
+        ctx.save_for_backward(x, w, b, scale, shift, mean, invstd, gram)
         ctx.conf = conf
-        ctx.xrelu = bool(xrelu)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, w, b, scale, shift, mean, invstd, gram, xsc, xsh = ctx.saved_tensors
+        x, w, b, scale, shift, mean, invstd, gram = ctx.saved_tensors
         training, relu, eps, momentum = ctx.conf
         N, H, W, C = x.shape
         K = w.shape[0]
@@ -1127,13 +1063,9 @@ class _C1BNFn(torch.autograd.Function):
         dgamma, dbeta = _empty((K,), F32, dev), _empty((K,), F32, dev)
         ws = _empty((lib.acfe_c1bn_workspace(M, C, K),), F32, dev)
         # eval mode: statistics are constants -> count -> inf removes the mean terms
-        args = (ptr(dy), ptr(x), M, C, ptr(w), K, ptr(b), ptr(scale), ptr(shift), ptr(mean), ptr(invstd), int(relu),
-                float(M) if training else 1e300, ptr(gram), ptr(dx), ptr(dw), ptr(db), ptr(dgamma), ptr(dbeta),
-                ptr(ws))
-        if xsc is not None:  # x is the BN input of the prologue; dx is the gradient for its output
-            call("acfe_c1bn_bwd_bn", *args, ptr(xsc), ptr(xsh), int(ctx.xrelu), stream())
-        else:
-            call("acfe_c1bn_bwd", *args, stream())
+        call("acfe_c1bn_bwd", ptr(dy), ptr(x), M, C, ptr(w), K, ptr(b), ptr(scale), ptr(shift), ptr(mean), ptr(invstd),
+             int(relu), float(M) if training else 1e300, ptr(gram), ptr(dx), ptr(dw), ptr(db), ptr(dgamma), ptr(dbeta),
+             ptr(ws), stream())
         return dx, dw, db, dgamma, dbeta, None, None, None
 
 
@@ -1152,15 +1084,29 @@ def conv_bn(x, w, b, gamma, beta, mmean, mvar, training, relu=True, stride=1, pa
 
 
 # ------------------------------------------------------------------ elementwise / pooling
+def _relu_bwd(g, z):
+    """g * [z > 0] for the ReLU output z; where the fused kernel takes the
+    shape, the result's channel sums ride along (_attach_sum)."""
+    d = torch.empty_like(g)
+    C = g.shape[-1]
+    if FUSE and g.dim() > 1 and _sums_ok(g) and _sums_ok(z) and _sums_ok(d):
+        rows = g.numel() // C
+        part = _empty((lib.acfe_reduce_blocks(rows), 2, C), F64, g.device)
+        call("acfe_relu_bwd_sum", ptr(g), ptr(z), rows, C, ptr(d), dtype_code(g.dtype), ptr(part), stream())
+        _attach_sum(d, part, rows)
+    else:
+        call("acfe_relu_bwd", ptr(g), ptr(z), g.numel(), ptr(d), dtype_code(g.dtype), stream())
+    return d
+
+
 class _AddFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, relu, want_stats, link):
         z = torch.empty_like(a)
-        stats = _no_stats(a.device)
         C = a.shape[-1]
+        rows = a.numel() // C
+        stats = _stats_slab(want_stats, lib.acfe_reduce_blocks(rows), C, a.device)
         if want_stats:
-            rows = a.numel() // C
-            stats = _empty((lib.acfe_reduce_blocks(rows), 2, C), F64, a.device)
             call("acfe_add_stats", ptr(a), ptr(b), rows, C, int(relu), ptr(z), dtype_code(a.dtype), ptr(stats),
                  stream())
         else:
@@ -1176,17 +1122,7 @@ class _AddFn(torch.autograd.Function):
     def backward(ctx, g, _gs):
         g = g.contiguous()
         if ctx.relu and not _tagged(g, "_acfe_relu_masked"):
-            (z,) = ctx.saved_tensors
-            d = torch.empty_like(g)
-            C = g.shape[-1]
-            if FUSE and g.dim() > 1 and _sums_ok(g) and _sums_ok(z) and _sums_ok(d):
-                rows = g.numel() // C
-                part = _empty((lib.acfe_reduce_blocks(rows), 2, C), F64, g.device)
-                call("acfe_relu_bwd_sum", ptr(g), ptr(z), rows, C, ptr(d), dtype_code(g.dtype), ptr(part), stream())
-                _attach_sum(d, part, rows)
-            else:
-                call("acfe_relu_bwd", ptr(g), ptr(z), g.numel(), ptr(d), dtype_code(g.dtype), stream())
-            g = d
+            g = _relu_bwd(g, ctx.saved_tensors[0])
         if ctx.link is not None:  # the shortcut input's gradient is added by the linked BN backward
             ctx.link.grad = g
             return g, None, None, None, None
@@ -1220,14 +1156,11 @@ class _ConvAddFn(torch.autograd.Function):
         ctx.bn = bn_src(x)
         N, H, W, C = x.shape
         K, R, S, _ = w.shape
-        _, pt = same_padding(H, R, 1)
-        _, pl = same_padding(W, S, 1)
+        _, _, pt, pl = _conv_geometry(H, W, R, S, 1, "same")
         wp = pack_weights(w, x.dtype, False)
         sc = sc.contiguous()
         z = _empty((N, H, W, K), x.dtype, x.device)
-        stats = _no_stats(x.device)
-        if want_stats:
-            stats = _empty((lib.acfe_conv2d_stats_rows(N * H * W, K), 2, wp.shape[0]), F64, x.device)
+        stats = _stats_slab(want_stats, lib.acfe_conv2d_stats_rows(N * H * W, K), wp.shape[0], x.device)
         pro = _pending(x) is not None and bn_prologue_ok(x.shape, x.dtype, w)
         if not pro:
             materialize(x)
@@ -1235,11 +1168,10 @@ class _ConvAddFn(torch.autograd.Function):
             if pro:  # x is a pending BN output: convolve it through the prologue, which also writes it
                 xr, scale, shift, brelu = _prologue_args(x)
                 call("acfe_conv2d_fwd_add_bn", ptr(xr), N, H, W, C, ptr(wp), K, pt, pl, ptr(b), ptr(sc), int(relu),
-                     ptr(z), ptr(stats) if want_stats else None, ptr(scale), ptr(shift), int(brelu), ptr(x),
-                     dtype_code(x.dtype), stream())
+                     ptr(z), ptr(stats), ptr(scale), ptr(shift), int(brelu), ptr(x), dtype_code(x.dtype), stream())
             else:
                 call("acfe_conv2d_fwd_add", ptr(x), N, H, W, C, ptr(wp), K, pt, pl, ptr(b), ptr(sc), int(relu),
-                     ptr(z), ptr(stats) if want_stats else None, dtype_code(x.dtype), stream())
+                     ptr(z), ptr(stats), dtype_code(x.dtype), stream())
         ctx.save_for_backward(x, w, z if relu else None)
         ctx.conf = (pt, pl, relu, b is not None, link)
         if relu:
@@ -1257,7 +1189,6 @@ class _ConvAddFn(torch.autograd.Function):
         x, w, z = ctx.saved_tensors
         pt, pl, relu, has_b, link = ctx.conf
         N, H, W, C = x.shape
-        K = w.shape[0]
         pend = _take_pending(g)
         if pend is None and ctx.fold is not None and ctx.fold.pending:
             # the BN left its dx unwritten for this node, but the gradient that
@@ -1277,18 +1208,10 @@ class _ConvAddFn(torch.autograd.Function):
                     link.grad = g
                     return dx, dw, db, None, None, None, None, None
                 return dx, dw, db, g, None, None, None, None
-            _apply_pending(g, pend)
+            _bn_bwd_apply(g, *pend)  # the fold does not take the node: g is written by the apply pass
         g = g.contiguous()
         if relu and not _tagged(g, "_acfe_relu_masked"):
-            d = torch.empty_like(g)
-            if _sums_ok(g) and _sums_ok(z) and _sums_ok(d):
-                rows = g.numel() // K
-                part = _empty((lib.acfe_reduce_blocks(rows), 2, K), F64, g.device)
-                call("acfe_relu_bwd_sum", ptr(g), ptr(z), rows, K, ptr(d), dtype_code(g.dtype), ptr(part), stream())
-                _attach_sum(d, part, rows)
-            else:
-                call("acfe_relu_bwd", ptr(g), ptr(z), g.numel(), ptr(d), dtype_code(g.dtype), stream())
-            g = d
+            g = _relu_bwd(g, z)
         dx, dw, db = _conv_bwd(x, w, g, 1, pt, pl, H, W, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
                                has_b and ctx.needs_input_grad[2], bias=ctx.bias, bn=ctx.bn)
         if link is not None:  # the shortcut input's gradient is added by the linked BN backward
@@ -1373,20 +1296,47 @@ def _maxpool_fwd(x, kh, kw, drop, want_stats):
     P, Q = H // kh, W // kw
     y = _empty((N, P, Q, C), x.dtype, x.device)
     amax = _empty((N, P, Q, C), torch.uint8, x.device)
-    stats = _no_stats(x.device)
-    if want_stats:
-        stats = _empty((lib.acfe_reduce_blocks(N * P * Q), 2, C), F64, x.device)
-    rate, seed = drop if drop is not None else (0.0, 0)
-    call("acfe_maxpool2d_fused", ptr(x), N, H, W, C, kh, kw, ptr(y), ptr(amax), float(rate), int(seed),
-         ptr(stats) if want_stats else None, dtype_code(x.dtype), stream())
+    stats = _stats_slab(want_stats, lib.acfe_reduce_blocks(N * P * Q), C, x.device)
+    rate, seed = _drop_args(drop)
+    call("acfe_maxpool2d_fused", ptr(x), N, H, W, C, kh, kw, ptr(y), ptr(amax), float(rate), int(seed), ptr(stats),
+         dtype_code(x.dtype), stream())
     return y, amax, stats
+
+
+def _bn_pool_fwd(x, saved, relu, kh, kw, want_stats):
+    """acfe_bn_maxpool2d_fused -> (y, argmax bytes, stats slab of y or empty):
+    MaxPool2D((kh, kw)) of the BN (+ReLU) of x, formed at load time from the
+    BN's `saved` (scale, shift, ...) and never stored."""
+    N, H, W, C = x.shape
+    P, Q = H // kh, W // kw
+    y = _empty((N, P, Q, C), x.dtype, x.device)
+    amax = _empty((N, P, Q, C), torch.uint8, x.device)
+    pst = _stats_slab(want_stats, lib.acfe_reduce_blocks(N * P * Q), C, x.device)
+    call("acfe_bn_maxpool2d_fused", ptr(x), N, H, W, C, ptr(saved[0]), ptr(saved[1]), int(relu), kh, kw, ptr(y),
+         ptr(amax), ptr(pst), dtype_code(x.dtype), stream())
+    return y, amax, pst
+
+
+def _pool_bwd_bn(x, amax, g, kh, kw, saved, relu):
+    """acfe_maxpool2d_bwd_argmax_bn -> (gu, part): the pooled gradient g
+    expanded to x's shape from the argmax bytes, and the reduce slab of the
+    backward of the BN (`saved`, relu) of x, which the kernel forms as well
+    (it reads x at the pixels it expands to): no separate reduce pass."""
+    N, H, W, C = x.shape
+    g = g.contiguous()
+    gu = _empty(x.shape, g.dtype, g.device)
+    part = _empty((lib.acfe_reduce_blocks(N * H * W) * 2 * C,), F64, x.device)
+    scale, shift, mean, invstd = saved
+    call("acfe_maxpool2d_bwd_argmax_bn", ptr(amax), ptr(g), N, H, W, C, kh, kw, ptr(gu), dtype_code(g.dtype),
+         ptr(x), ptr(scale), ptr(shift), ptr(mean), ptr(invstd), int(relu), ptr(part), stream())
+    return gu, part
 
 
 def _maxpool_bwd(amax, g, shape, kh, kw, drop):
     N, H, W, C = shape
     g = g.contiguous()
     dx = _empty(shape, g.dtype, g.device)
-    rate, seed = drop if drop is not None else (0.0, 0)
+    rate, seed = _drop_args(drop)
     call("acfe_maxpool2d_bwd_argmax", ptr(amax), ptr(g), N, H, W, C, kh, kw, float(rate), int(seed), ptr(dx),
          dtype_code(g.dtype), stream())
     return dx
@@ -1438,15 +1388,7 @@ class _BNPoolFn(torch.autograd.Function):
         kh, kw, training, relu, eps, momentum, want_stats = conf
         _, saved = _bn_fwd(x, gamma, beta, stats if training else None, mmean, mvar, training, relu, eps, momentum,
                            None)
-        N, H, W, C = x.shape
-        P, Q = H // kh, W // kw
-        y = _empty((N, P, Q, C), x.dtype, x.device)
-        amax = _empty((N, P, Q, C), torch.uint8, x.device)
-        pst = _no_stats(x.device)
-        if want_stats:
-            pst = _empty((lib.acfe_reduce_blocks(N * P * Q), 2, C), F64, x.device)
-        call("acfe_bn_maxpool2d_fused", ptr(x), N, H, W, C, ptr(saved[0]), ptr(saved[1]), int(relu), kh, kw, ptr(y),
-             ptr(amax), ptr(pst) if want_stats else None, dtype_code(x.dtype), stream())
+        y, amax, pst = _bn_pool_fwd(x, saved, relu, kh, kw, want_stats)
         ctx.save_for_backward(x, amax, *saved)
         ctx.conf = conf
         ctx.mark_non_differentiable(pst)
@@ -1457,19 +1399,10 @@ class _BNPoolFn(torch.autograd.Function):
         x, amax, *saved = ctx.saved_tensors
         kh, kw, training, relu, eps, momentum, want_stats = ctx.conf
         if FUSE_BN_REDUCE and _sums_ok(x):
-            # the pool backward also forms the BN backward's reduce slab (it
-            # reads x at the pixels it expands to): no separate reduce pass
-            N, H, W, C = x.shape
-            g = g.contiguous()
-            gu = _empty(x.shape, g.dtype, g.device)
-            part = _empty((lib.acfe_reduce_blocks(N * H * W) * 2 * C,), F64, x.device)
-            scale, shift, mean, invstd = saved
-            call("acfe_maxpool2d_bwd_argmax_bn", ptr(amax), ptr(g), N, H, W, C, kh, kw, ptr(gu), dtype_code(g.dtype),
-                 ptr(x), ptr(scale), ptr(shift), ptr(mean), ptr(invstd), int(relu), ptr(part), stream())
-            dx, dgamma, dbeta = _bn_bwd(x, gu, saved, relu, training, params=ctx.gb, part=part)
+            gu, part = _pool_bwd_bn(x, amax, g, kh, kw, saved, relu)
         else:
-            gu = _maxpool_bwd(amax, g, x.shape, kh, kw, None)
-            dx, dgamma, dbeta = _bn_bwd(x, gu, saved, relu, training, params=ctx.gb)
+            gu, part = _maxpool_bwd(amax, g, x.shape, kh, kw, None), None
+        dx, dgamma, dbeta = _bn_bwd(x, gu, saved, relu, training, params=ctx.gb, part=part)
         return dx, dgamma, dbeta, None, None, None, None
 
 
@@ -1562,8 +1495,8 @@ class _ConvPoolBNFn(torch.autograd.Function):
         wp = pack_weights(w, x.dtype, False)
         u = _empty((N, H // 2, W // 2, K), x.dtype, dev)
         amax = _empty((N, H // 2, W // 2, K), torch.uint8, dev)
-        stats = _empty((lib.acfe_conv2d_stats_rows(N * H * W, K), 2, wp.shape[0]), F64, dev) if training else None
-        r_, s_ = drop if drop is not None else (0.0, 0)
+        stats = _stats_slab(training, lib.acfe_conv2d_stats_rows(N * H * W, K), wp.shape[0], dev)
+        r_, s_ = _drop_args(drop)
         with _Timed(w, "fwd"):
             if pro:  # x is a pending BN output: the conv applies it while staging and writes it
                 xr, scale, shift, brelu = _prologue_args(x)
@@ -1600,21 +1533,14 @@ class _ConvPoolBNFn(torch.autograd.Function):
                 call("acfe_conv2d_dgrad_unpool", ptr(g), ptr(amax), N, H, W, K, ptr(wf), C, pt, pl, ptr(dx),
                      dtype_code(x.dtype), s)
         if ctx.needs_input_grad[1]:
-            tgt = direct_grad(w)
-            dw = tgt if tgt is not None else _empty(w.shape, F32, dev)
+            dwt, beta = _grad_into(w)
             ws = _empty((lib.acfe_conv2d_wgrad_workspace(N, H, W, C, K, 3, 3, H, W),), F32, dev)
             with _Timed(w, "wgrad"):
-                call("acfe_conv2d_wgrad_unpool", ptr(x), N, H, W, C, ptr(g), ptr(amax), K, pt, pl, ptr(dw),
-                     1.0 if tgt is not None else 0.0, dtype_code(x.dtype), ptr(ws), s)
-            if tgt is not None:
-                dw = None
-                grads_ready(w)
+                call("acfe_conv2d_wgrad_unpool", ptr(x), N, H, W, C, ptr(g), ptr(amax), K, pt, pl, ptr(dwt), beta,
+                     dtype_code(x.dtype), ptr(ws), s)
+            dw = _grad_out(w, dwt, beta)
         if ctx.has_b and ctx.needs_input_grad[2]:
-            tb = direct_grad(ctx.bias)  # the pool backward scatters: sum of the pooled gradient
-            db = channel_sum(g, K, into=tb)
-            if tb is not None:
-                db = None
-                grads_ready(ctx.bias)
+            db = _bias_grad(g, K, ctx.bias)  # the pool backward scatters: sum of the pooled gradient
         return dx, dw, db, dgamma, dbeta, None, None, None
 
 
@@ -1628,9 +1554,7 @@ def conv_maxpool_dropout_bn(x, w, b, stride, padding, kh, kw, gamma, beta, mmean
         return maxpool_dropout_bn(y, kh, kw, gamma, beta, mmean, mvar, training, rate, seed, relu, eps, momentum)
     if training and rate > 0.0 and seed is None:
         seed = next_seed()
-    K, R, S, _ = w.shape
-    _, pt = same_padding(x.shape[1], R, 1)
-    _, pl = same_padding(x.shape[2], S, 1)
+    _, _, pt, pl = _conv_geometry(x.shape[1], x.shape[2], w.shape[1], w.shape[2], 1, "same")
     conf = (pt, pl, float(rate), int(seed or 0), bool(training), bool(relu), float(eps), float(momentum),
             bool(defer))
     return _ConvPoolBNFn.apply(x, w, b, gamma, beta, mmean, mvar, conf)

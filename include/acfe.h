@@ -469,21 +469,6 @@ int acfe_c1bn_bwd(const void* dy, const void* x, long long M, int C, const float
                   const float* scale, const float* shift, const float* mean, const float* invstd, int relu,
                   double count, const float* gram, void* dx, float* dw, float* db, float* dgamma, float* dbeta,
                   float* workspace, void* stream);
-/* The three passes with a BatchNormalization (+ReLU) prologue on x (the
- * stride-2 block's bn2a0 -> ReLU in front of branch2a0, resnet/wr_resnet_bird.py
- * :121-127): x is the BN INPUT, every pass forms x' = (ReLU)(x * x_scale +
- * x_shift) (fp32 [16] from acfe_bn_finalize; acfe_bn_apply's values) and x' is
- * never stored; dx is the gradient for x'. */
-int acfe_c1bn_stats_bn(const void* x, long long M, int C, const float* w, int K, const float* bias, double* part,
-                       float* gram, float* workspace, const float* x_scale, const float* x_shift, int x_relu,
-                       void* stream);
-int acfe_c1bn_apply_bn(const void* x, long long M, int C, const float* w, int K, const float* bias,
-                       const float* scale, const float* shift, int relu, void* y, const float* x_scale,
-                       const float* x_shift, int x_relu, void* stream);
-int acfe_c1bn_bwd_bn(const void* dy, const void* x, long long M, int C, const float* w, int K, const float* bias,
-                     const float* scale, const float* shift, const float* mean, const float* invstd, int relu,
-                     double count, const float* gram, void* dx, float* dw, float* db, float* dgamma, float* dbeta,
-                     float* workspace, const float* x_scale, const float* x_shift, int x_relu, void* stream);
 
 /* acfe_bn_bwd_apply_ex whose residual term is the backward of
  * AveragePooling2D(k, strides=k, "same") applied to x (the conv shortcut of the
