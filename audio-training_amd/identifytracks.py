@@ -12,6 +12,13 @@ scipy.ndimage min / max filters --; 8-connected components give time /
 frequency boxes, which are filtered by size, then merged into tracks
 (merge_signals, get_tracks_from_signals) with the reference's thresholds.
 
+get_end and signal_noise also exist on the device (acfe/tracks.py over
+csrc/tracks.hip, `predict.py --detector gpu`): there the map comes back as
+horizontal runs, which boxes_from_runs unions into the same components, and
+both paths end in signals_from_stats, the size filter and time / frequency
+scaling factored out of signal_noise.  The functions here stay the host
+detector and the reference the device one is tested against.
+
 cv2 / librosa are not in the image: the morphology and the STFT are restated
 from their published definitions (parity unpinned beyond that; the tests pin
 the component boxes on synthetic recordings with known chirps).
@@ -172,6 +179,82 @@ def _box_min(a, h, w):
     return minimum_filter(a, size=_box(h, w), mode="constant", cval=1)
 
 
+def box_geometry(sr, hop_length=281, n_fft=2048):
+    """(freqs, height, width) of signal_noise (:58-71, :94-95): the bin
+    frequencies, the first bin above 100 Hz (+1) and 0.25 s of frames -- the
+    dilation box, and the base of the size filter."""
+    freqs = np.fft.rfftfreq(n_fft, 1.0 / sr)
+    height = 0
+    for i, f in enumerate(freqs):
+        if f > 100:
+            height = i + 1
+            break
+    return freqs, height, int(SIGNAL_WIDTH * sr / hop_length)
+
+
+def signals_from_stats(stats, sr, freqs, height, width, min_width=None, min_height=None):
+    """The tail of signal_noise (:113-142): component stats (left, top, width,
+    height, area), already sorted by left, -> the Signals that pass the size
+    filter.  Shared by the host detector and the device one (acfe/tracks.py)."""
+    if min_height is None:
+        min_height = height - height // 10
+    if min_width is None:
+        min_width = 0.65 * width
+    signals = []
+    for s in stats:
+        if not (s[2] > min_width and s[3] > min_height):
+            continue
+        max_freq = min(len(freqs) - 1, s[1] + s[3])
+        signals.append(Signal(s[0] * 281 / sr, (s[0] + s[2]) * 281 / sr, freqs[s[1]], freqs[max_freq], s[4]))
+    return signals
+
+
+def boxes_from_runs(runs):
+    """8-connected components of a binary map given as its horizontal runs
+    (row, first col, last col), in any order -> [(left, top, width, height,
+    area)] as cv2.connectedComponentsWithStats gives them (:104), sorted by
+    left with ties in raster order of each component's first cell (the order
+    signal_noise's stable sort of the label order leaves).  Runs of adjacent
+    rows are joined when their column ranges touch or overlap diagonally."""
+    runs = np.asarray(runs, np.int64).reshape(-1, 3)
+    n = len(runs)
+    if n == 0:
+        return []
+    runs = runs[np.lexsort((runs[:, 1], runs[:, 0]))]  # raster order
+    row, first, last = (runs[:, k].tolist() for k in range(3))
+    parent = list(range(n))
+
+    def find(i):
+        while parent[i] != i:
+            parent[i] = parent[parent[i]]
+            i = parent[i]
+        return i
+
+    j = 0  # first run of the row above that can still reach run i
+    for i in range(n):
+        while row[j] < row[i] - 1 or (row[j] == row[i] - 1 and last[j] < first[i] - 1):
+            j += 1
+        k = j
+        while k < i and row[k] == row[i] - 1 and first[k] <= last[i] + 1:
+            a, b = find(k), find(i)
+            if a != b:  # the smaller index stays the root: a component's root is its first run in raster order
+                parent[max(a, b)] = min(a, b)
+            k += 1
+    root = np.array([find(i) for i in range(n)])
+    ids, comp = np.unique(root, return_inverse=True)  # ascending roots = raster order of the first cells
+    m = len(ids)
+    left, top = np.full(m, np.iinfo(np.int64).max), np.full(m, np.iinfo(np.int64).max)
+    right, bottom, area = np.full(m, -1), np.full(m, -1), np.zeros(m, np.int64)
+    np.minimum.at(left, comp, runs[:, 1])
+    np.maximum.at(right, comp, runs[:, 2])
+    np.minimum.at(top, comp, runs[:, 0])
+    np.maximum.at(bottom, comp, runs[:, 0])
+    np.add.at(area, comp, runs[:, 2] - runs[:, 1] + 1)
+    order = np.argsort(left, kind="stable")
+    return [(int(left[c]), int(top[c]), int(right[c] - left[c] + 1), int(bottom[c] - top[c] + 1), int(area[c]))
+            for c in order]
+
+
 def signal_noise(frames, sr, hop_length=281, n_fft=1024, min_width=None, min_height=None, spectogram=None):
     """identifytracks.signal_noise (:51-143) -> (signals, |STFT|).  The
     reference overrides n_fft with 2048 (:55); so does this."""
@@ -180,18 +263,12 @@ def signal_noise(frames, sr, hop_length=281, n_fft=1024, min_width=None, min_hei
     n_fft = 2048
     if spectogram is None:
         spectogram = stft_magnitude(frames, n_fft, hop_length)
-    freqs = np.fft.rfftfreq(n_fft, 1.0 / sr)
-    height = 0
-    for i, f in enumerate(freqs):  # first bin above 100 Hz (+1)
-        if f > 100:
-            height = i + 1
-            break
+    freqs, height, width = box_geometry(sr, hop_length, n_fft)
     spec = spectogram / np.amax(spectogram)
     row_med = np.median(spec, axis=1)[:, None]
     col_med = np.median(spec, axis=0)[None, :]
     signal = ((spec > 2 * col_med) & (spec > 3 * row_med)).astype(np.uint8)
     signal = _box_max(_box_min(signal, 4, 4), 4, 4)  # MORPH_OPEN, 4x4
-    width = int(SIGNAL_WIDTH * sr / hop_length)
     signal = _box_max(signal, height, width)
     signal = _box_min(signal, height // 10, width)
     lab, n = label(signal, structure=np.ones((3, 3), np.uint8))  # 8-connectivity
@@ -204,17 +281,7 @@ def signal_noise(frames, sr, hop_length=281, n_fft=1024, min_width=None, min_hei
             top, left = sl[0].start, sl[1].start
             stats.append((left, top, sl[1].stop - left, sl[0].stop - top, int(area[k])))
     stats.sort(key=lambda s: s[0])
-    if min_height is None:
-        min_height = height - height // 10
-    if min_width is None:
-        min_width = 0.65 * width
-    signals = []
-    for s in stats:
-        if not (s[2] > min_width and s[3] > min_height):
-            continue
-        max_freq = min(len(freqs) - 1, s[1] + s[3])
-        signals.append(Signal(s[0] * 281 / sr, (s[0] + s[2]) * 281 / sr, freqs[s[1]], freqs[max_freq], s[4]))
-    return signals, spectogram
+    return signals_from_stats(stats, sr, freqs, height, width, min_width, min_height), spectogram
 
 
 def merge_signals(signals):

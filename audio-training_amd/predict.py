@@ -2,14 +2,18 @@
 """Inference driver of the acfe path (reference predict.py:726-967,
 predict_utils.py:9-239).
 
-  python predict.py --file REC.wav CHECKPOINT_DIR [--stride 1] [--batch-size 1024]
+  python predict.py --file REC.wav CHECKPOINT_DIR [--stride 1] [--batch-size 1024] [--detector gpu]
 
 The recording is decoded on the host (WAV via scipy; the reference's ffmpeg /
 librosa loader is out of scope) and resampled to 48 kHz.
 
 --mode tracks (default, the reference's predict.py:735-956): the digitally
-silent tail is cut (get_end), signals are detected and merged into tracks on
-the host (identifytracks.py), each track is cut into 3 s windows at a 1 s
+silent tail is cut (get_end) and signals are detected -- on the host with
+numpy (--detector host, the default) or on the GPU (--detector gpu: the
+recording is uploaded once and acfe.tracks runs the STFT, the medians, the
+morphology and the run extraction as HIP kernels, returning the same signals
+for the same spectrogram) --, the signals are merged into tracks on the host
+(identifytracks.py), each track is cut into 3 s windows at a 1 s
 stride (predict_utils.load_samples:59-150: short tracks centred in a 3 s
 window, partial windows zero padded at a random offset), the windows of all
 tracks go to the GPU as one batch (normalize, librosa-style centred STFT with
@@ -128,15 +132,31 @@ def track_windows(frames, sr, tracks, segment_length=3, stride=1, fmin=100, fmax
     return out
 
 
-def detect_tracks(frames, sr=SR):
+def detect_tracks(frames, sr=SR, detector="host"):
     """predict.main (:735-740): cut the silent tail, detect signals, merge
-    them into tracks -> (tracks, frames[:end], end seconds)."""
+    them into tracks -> (tracks, frames[:end], end seconds).  detector "host"
+    runs identifytracks on numpy; "gpu" (or an acfe.tracks.SignalDetector to
+    reuse) uploads the recording once and runs get_end and signal_noise on
+    the device, the cut recording being a slice of that one buffer.  The
+    merging into tracks is host work on a few hundred boxes either way."""
     from identifytracks import get_end, get_tracks_from_signals, signal_noise
 
-    end = get_end(frames, sr)
-    frames = frames[: int(sr * end)]
-    signals, _ = signal_noise(frames, sr)
-    return get_tracks_from_signals(signals, end), frames, end
+    if detector == "host":
+        end = get_end(frames, sr)
+        frames = frames[: int(sr * end)]
+        signals, _ = signal_noise(frames, sr)
+        return get_tracks_from_signals(signals, end), frames, end
+    if detector == "gpu":
+        from acfe.tracks import SignalDetector
+
+        detector = SignalDetector(sr=sr)
+    elif isinstance(detector, str):
+        raise ValueError(f"detector {detector!r}: expected 'host' or 'gpu'")
+    dev = detector.upload(frames)
+    end = detector.get_end(dev)
+    cut = int(sr * end)
+    signals = detector.signal_noise(dev[:cut])[0] if cut else []
+    return get_tracks_from_signals(signals, end), frames[:cut], end
 
 
 class Predictor:
@@ -167,6 +187,7 @@ class Predictor:
                 raise FileNotFoundError(f"{d}: no model.pt, *.keras or *.weights.h5")
             load_keras_weights(self.model, cands[0])
         holder.to(self.device).eval()
+        self._detector = None  # acfe.tracks.SignalDetector of predict_tracks(detector="gpu")
 
     @torch.no_grad()
     def predict_windows(self, recording: np.ndarray, stride=1.0, batch_size=1024, pad_mode="constant"):
@@ -199,9 +220,16 @@ class Predictor:
             out.append(ops.sigmoid(self.model(self.frontend(x, pad_mode="constant"))))
         return torch.cat(out).float().cpu().numpy()
 
-    def predict_tracks(self, frames, threshold=None, batch_size=1024, rng=None):
-        """Tracks of one recording with their ModelResult (predict.py:735-956)."""
-        tracks, frames, end = detect_tracks(np.asarray(frames, np.float32))
+    def predict_tracks(self, frames, threshold=None, batch_size=1024, rng=None, detector="host"):
+        """Tracks of one recording with their ModelResult (predict.py:735-956);
+        `detector` as in detect_tracks ("gpu" keeps one SignalDetector per Predictor)."""
+        if detector == "gpu":
+            if self._detector is None:
+                from acfe.tracks import SignalDetector
+
+                self._detector = SignalDetector(device=self.device, sr=SR)
+            detector = self._detector
+        tracks, frames, end = detect_tracks(np.asarray(frames, np.float32), detector=detector)
         thresh = self.meta.get("threshold", 0.7) if threshold is None else threshold
         wins = track_windows(frames, SR, tracks, rng=rng)
         counts = [len(w) for w in wins]
@@ -242,12 +270,14 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=1024)
     ap.add_argument("--threshold", type=float, default=0.7)
     ap.add_argument("--mode", choices=("tracks", "windows"), default="tracks")
+    ap.add_argument("--detector", choices=("host", "gpu"), default="host",
+                    help="track detection (--mode tracks): numpy on the host, or the HIP kernels of acfe.tracks")
     a = ap.parse_args(argv)
     p = Predictor(a.model)
     for f in a.file:
         t0 = time.perf_counter()
         if a.mode == "tracks":
-            tracks, end = p.predict_tracks(load_recording(f), a.threshold, a.batch_size)
+            tracks, end = p.predict_tracks(load_recording(f), a.threshold, a.batch_size, detector=a.detector)
             r = {"file": str(f), "end": end, "tracks": [t.get_meta() for t in tracks]}
         else:
             r = p.predict_file(f, a.stride, a.batch_size, a.threshold)

@@ -29,6 +29,12 @@
  *   acfe_pcen_fwd          tfpcen.py:33-39,89-99     ExponentialMovingAverage + PCEN.call
  *   acfe_pcen_normalize    tfpcen.py:105-110         normalize_minmax (batch-global)
  *   acfe_pcen_bwd          gradient of the three above w.r.t. gain/bias/root/smooth
+ *   acfe_stft_mag          identifytracks.py:57,78   |librosa.stft| of a recording + np.amax
+ *   acfe_median            identifytracks.py:80-81   np.median along either axis
+ *   acfe_signal_map        identifytracks.py:79,89-91  the two-median threshold
+ *   acfe_morph_box         identifytracks.py:92,98-99  cv2 open / dilate / erode
+ *   acfe_map_runs          identifytracks.py:104     connectedComponentsWithStats (runs; host union)
+ *   acfe_chunk_flat        identifytracks.py:41-43   get_end's max == min chunk test
  */
 #ifndef ACFE_H
 #define ACFE_H
@@ -563,6 +569,57 @@ int acfe_loss(const float* z, const float* y, int B, int L, int mode, float grad
  * parameter arena; alpha = lr*sqrt(1-b2^t)/(1-b1^t). */
 int acfe_adam_step(float* params, const float* grads, float* m, float* v, long long n, float grad_scale,
                    float beta1, float beta2, float eps, float alpha, void* stream);
+
+/* ---- Track detection of the predict path (csrc/tracks.hip): the device form
+ * of identifytracks.get_end (identifytracks.py:21-48) and signal_noise
+ * (:51-143).  Images are row-major [rows][cols] = [frequency bin][frame] and
+ * are indexed in 64 bits (1025 x T passes 2^31 at about 3.3 hours of audio). */
+
+/* |librosa.stft(x, n_fft, hop)| of one whole recording (identifytracks.py:57:
+ * centred, constant padding, periodic Hann): x float[n] -> spec
+ * [1 + n_fft/2][T] fp32, T = 1 + n / hop, rows written in 64-B runs.  A frame
+ * that touches no sample is exactly 0 in every bin.  max_out: one float, the
+ * maximum of spec (np.amax, :78).  ws: acfe_stft_mag_workspace(n, n_fft, hop)
+ * bytes.  Only n_fft = 2048 (:55) is supported; any other size is
+ * ACFE_E_INVAL, from both calls. */
+int64_t acfe_stft_mag_workspace(int64_t n, int n_fft, int hop);
+int acfe_stft_mag(const float* x, int64_t n, int n_fft, int hop, float* spec, float* max_out, void* ws,
+                  void* stream);
+
+/* np.median(img / scale[0], axis) (identifytracks.py:80-81) by exact selection
+ * on img itself: the middle order statistic divided by scale for an odd count,
+ * (a / scale + b / scale) / 2 of the two middle ones for an even count, in
+ * float32.  axis 1: out[rows], one median per row (radix select, four
+ * histogram passes over the row); axis 0: out[cols], one per column (the
+ * order statistic built bit by bit).  img must be finite and non-negative
+ * (the selection orders bit patterns); scale NULL = 1. */
+int acfe_median(const float* img, int rows, int cols, int axis, const float* scale, float* out, void* stream);
+
+/* map[r][c] = (s > 2 col_med[c]) & (s > 3 row_med[r]) with s = spec[r][c] /
+ * max[0] in float32 (identifytracks.py:79,89-91), as uint8 0 / 1. */
+int acfe_signal_map(const float* spec, int rows, int cols, const float* max, const float* col_med,
+                    const float* row_med, uint8_t* map, void* stream);
+
+/* cv2.erode (op 0) / cv2.dilate (op 1) of a 0 / 1 uint8 map with an h x w box
+ * (identifytracks.py:92,98-99): window rows y - h/2 .. y - h/2 + h - 1,
+ * columns likewise, out-of-image cells ignored; h <= 0 or w <= 0 is OpenCV's
+ * 3 x 3 default.  dst != src; ws: acfe_morph_box_workspace(rows, cols) bytes. */
+int64_t acfe_morph_box_workspace(int rows, int cols);
+int acfe_morph_box(const uint8_t* src, int rows, int cols, int h, int w, int op, uint8_t* dst, void* ws,
+                   void* stream);
+
+/* The horizontal runs of a 0 / 1 map, {row, first col, last col} int32
+ * triples in no particular order, from which the host forms the 8-connected
+ * components of cv2.connectedComponentsWithStats (identifytracks.py:104).
+ * count[0] (device int32, reset by the call) receives the number of runs the
+ * map holds; only the first `cap` found are stored, so count[0] > cap tells
+ * the caller the size to retry with. */
+int acfe_map_runs(const uint8_t* map, int rows, int cols, int* runs, int cap, int* count, void* stream);
+
+/* get_end's silence test (identifytracks.py:41-43): flags[c] = 1 when the
+ * max of img[:, c*chunk : (c+1)*chunk] equals its min, else 0, for c <
+ * n_chunks (n_chunks * chunk <= cols). */
+int acfe_chunk_flat(const float* img, int rows, int cols, int chunk, int n_chunks, int* flags, void* stream);
 
 #ifdef __cplusplus
 }
