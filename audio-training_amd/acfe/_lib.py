@@ -134,6 +134,7 @@ SIGNATURES: dict[str, list] = {
     "acfe_morph_box": [P, I32, I32, I32, I32, I32, P, P, P],
     "acfe_map_runs": [P, I32, I32, P, I32, P, P],
     "acfe_chunk_flat": [P, I32, I32, I32, I32, P, P],
+    "acfe_windows_normalize": [P, I64, P, I32, I32, P, P, P],
 }
 _RESTYPES = {"acfe_last_error": C.c_char_p, "acfe_conv2d_wgrad_workspace": I64, "acfe_conv2d_dgrad_workspace": I64, "acfe_crc32c": C.c_uint32,
              "acfe_c1bn_workspace": I64, "acfe_stft_mag_workspace": I64, "acfe_morph_box_workspace": I64}

@@ -144,6 +144,40 @@ def normalize(x: torch.Tensor) -> torch.Tensor:
     return normalize_apply(x, normalize_stats(x))
 
 
+def normalize_windows(rec: torch.Tensor, plan, n: int, out: torch.Tensor | None = None,
+                      stats: torch.Tensor | None = None) -> torch.Tensor:
+    """The normalised windows [n_windows, n] that the host table `plan`
+    ((src, count, pad) rows, predict.track_window_plan) cuts from the 1-D fp32
+    device recording `rec`: tfdataset.normalize of each zero-padded window
+    v[i] = rec[src + i - pad] (pad <= i < pad + count, 0 elsewhere),
+    bit-identical to normalize() of the windows cut on the host.  The table
+    is validated on the host (predict.check_window_plan) before it is
+    uploaded.  `stats` [n_windows, 2] receives {min, max - min} per window
+    when given."""
+    from predict import check_window_plan  # host-only index arithmetic, next to track_window_plan
+
+    require_cuda(rec, out, stats)
+    if rec.dtype != torch.float32 or rec.dim() != 1 or not rec.is_contiguous():
+        raise TypeError("the recording must be a contiguous 1-D float32 tensor")
+    n = int(n)
+    if n <= 0:
+        raise ValueError("n must be positive")
+    plan = check_window_plan(plan, rec.numel(), n)
+    batch = plan.shape[0]
+    if out is None:
+        out = torch.empty((batch, n), dtype=torch.float32, device=rec.device)
+    elif tuple(out.shape) != (batch, n) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("bad out tensor")
+    if stats is not None and (tuple(stats.shape) != (batch, 2) or stats.dtype != torch.float32
+                              or not stats.is_contiguous()):
+        raise ValueError("bad stats tensor")
+    if batch == 0:
+        return out
+    dplan = torch.from_numpy(plan).to(rec.device)
+    call("acfe_windows_normalize", ptr(rec), rec.numel(), ptr(dplan), batch, n, ptr(out), ptr(stats), stream())
+    return out
+
+
 def mix_up(x1, x2, lam, stats1=None, stats2=None) -> torch.Tensor:
     """tfdataset.mix_up image blend (tfdataset.py:950); lam [B] fp32 on device."""
     require_cuda(x1, x2, lam, stats1, stats2)

@@ -52,10 +52,16 @@ class FrontEnd(nn.Module):
         # Normalise once into a scratch clip (frames overlap ~14.6x, so
         # normalising on load inside the STFT repeats the divide per frame).
         src = fe.normalize_apply(src, st, out=src if src is not x1 else None)
+        return self.features(src, pad_mode, scope_minmax)
+
+    def features(self, src_normalised, pad_mode="end", scope_minmax=None):
+        """The tail of forward: already normalised clips [B, N] fp32 (forward's
+        scratch clip, or frontend.normalize_windows' output) -> model input."""
         if self.pcen is not None:
-            mel = self.plan.mel(src, None, pad_mode=pad_mode, power=self.power, layout="btm", timer=self.timer)
+            mel = self.plan.mel(src_normalised, None, pad_mode=pad_mode, power=self.power, layout="btm",
+                                timer=self.timer)
             return self.pcen(mel, scope_minmax)
-        mel = self.plan.mel(src, None, pad_mode=pad_mode, power=self.power, layout="bmt", timer=self.timer)
+        mel = self.plan.mel(src_normalised, None, pad_mode=pad_mode, power=self.power, layout="bmt", timer=self.timer)
         return ops.cast(mel, self.dtype)
 
 

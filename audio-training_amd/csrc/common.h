@@ -55,6 +55,17 @@ __device__ __forceinline__ double wave_sumd(double v) {
   return v;
 }
 
+// One sample of tfdataset.normalize (tfdataset.py:1927-1931) from the clip's
+// {min, max - min}: float32, same order: -min, /max, +1e-6, -0.5, *2.  Shared by
+// the front end (frontend.hip) and the window cutter (windows.hip).
+__device__ __forceinline__ float norm1(float v, float mn, float rng) {
+  float t = __fsub_rn(v, mn);
+  t = __fdiv_rn(t, rng);
+  t = __fadd_rn(t, 0.000001f);
+  t = __fsub_rn(t, 0.5f);
+  return __fmul_rn(t, 2.0f);
+}
+
 // Counter-based RNG (splitmix-style hash) for dropout masks: deterministic in
 // (seed, index), so the backward regenerates the forward's mask.
 __device__ __forceinline__ uint32_t hash_u32(uint64_t seed, uint64_t idx) {

@@ -227,14 +227,6 @@ __device__ __forceinline__ float norm1r(float v, float mn, float rng, float rinv
   q = __fsub_rn(q, 0.5f);
   return __fmul_rn(q, 2.0f);
 }
-__device__ __forceinline__ float norm1(float v, float mn, float rng) {
-  // tfdataset.py:1927-1931, float32, same order: -min, /max, +1e-6, -0.5, *2
-  float t = __fsub_rn(v, mn);
-  t = __fdiv_rn(t, rng);
-  t = __fadd_rn(t, 0.000001f);
-  t = __fsub_rn(t, 0.5f);
-  return __fmul_rn(t, 2.0f);
-}
 
 ACFE_API int acfe_normalize_stats(const float* x, int64_t cs, int batch, int n, float* stats,
                                   void* stream) {

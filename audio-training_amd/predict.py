@@ -3,6 +3,7 @@
 predict_utils.py:9-239).
 
   python predict.py --file REC.wav CHECKPOINT_DIR [--stride 1] [--batch-size 1024] [--detector gpu]
+                    [--windows device]
 
 The recording is decoded on the host (WAV via scipy; the reference's ffmpeg /
 librosa loader is out of scope) and resampled to 48 kHz.
@@ -19,7 +20,13 @@ window, partial windows zero padded at a random offset), the windows of all
 tracks go to the GPU as one batch (normalize, librosa-style centred STFT with
 constant padding, |X|^2, mel, PCEN: predict_utils.get_spect) and the mean
 sigmoid output per track is thresholded at 0.7, else the argmax becomes the
-raw tag (predict.py:931-956).
+raw tag (predict.py:931-956).  With --windows device the host computes only
+where each window lies (track_window_plan: source sample, length and left
+padding per window, the same arithmetic and the same random offsets) and one
+HIP kernel cuts, zero pads and normalises the windows straight out of the
+uploaded recording -- with --detector gpu the buffer the detector already
+holds -- so no window passes through host memory; the predictions are those
+of --windows host, which stays the default.
 
 --mode windows: the recording is uploaded once and 3 s windows every
 `stride` seconds are read in place by the fused front-end kernel; the
@@ -132,13 +139,91 @@ def track_windows(frames, sr, tracks, segment_length=3, stride=1, fmin=100, fmax
     return out
 
 
-def detect_tracks(frames, sr=SR, detector="host"):
+def track_window_plan(n_frames, sr, tracks, segment_length=3, stride=1, fmin=100, fmax=11000, pad_short_tracks=False,
+                      rng=None):
+    """track_windows as a table instead of copies: the windows it would cut
+    from a recording of n_frames samples -> (plan, counts).  plan is int64
+    [n_windows, 3] with rows (src, count, pad): window w is
+    v[i] = frames[src + i - pad] for pad <= i < pad + count and 0 elsewhere,
+    i < n = int(sr * segment_length).  counts[k] is the number of windows of
+    track k (0 for tracks outside [fmin, fmax]).  The arithmetic is
+    track_windows' own, its numpy slices clipped as numpy clips them, and
+    rng.randint is drawn once per partial window in the same order, so that
+    applying the plan reproduces track_windows bit for bit.  An empty window
+    (count 0) has src 0."""
+    rng = rng if rng is not None else np.random
+    sample_size = int(sr * segment_length)
+    rows, counts = [], []
+    for t in tracks:
+        if t.freq_start is not None and t.freq_end is not None and (t.freq_start > fmax or t.freq_end < fmin):
+            counts.append(0)
+            continue
+        start, end = 0, segment_length
+        sr_end, sr_start = int(t.end * sr), int(sr * t.start)
+        if pad_short_tracks:
+            end = min(end, t.length)
+        else:
+            missing = sample_size - (sr_end - sr_start)
+            if missing > 0:
+                offset = missing // 2
+                sr_start -= offset
+                if sr_start <= 0:
+                    sr_start = 0
+                    sr_end = min(sample_size, n_frames)
+                else:
+                    end_offset = sr_end + missing - offset
+                    if end_offset > n_frames:
+                        end_offset = n_frames
+                        sr_start = max(end_offset - sample_size, 0)
+                    sr_end = end_offset
+        # track_frames = frames[sr_start:sr_end]: samples [t0, t0 + t_len) of the recording
+        t0, t1, _ = slice(sr_start, sr_end).indices(n_frames)
+        t_len = max(0, t1 - t0)
+        sr_start, sr_end = 0, min(sr_end, sample_size)
+        n_win = 0
+        while True:
+            w0, w1, _ = slice(sr_start, sr_end).indices(t_len)  # track_frames[sr_start:sr_end]
+            count = max(0, w1 - w0)
+            pad = int(rng.randint(0, sample_size - count)) if count != sample_size else 0
+            rows.append((t0 + w0 if count else 0, count, pad))
+            n_win += 1
+            start += stride
+            end = start + segment_length
+            sr_start = int(start * sr)
+            sr_end = min(int(end * sr), sr_start + sample_size)
+            if end > t.length:
+                break
+        counts.append(n_win)
+    return np.array(rows, np.int64).reshape(-1, 3), counts
+
+
+def check_window_plan(plan, rec_len, n):
+    """A window table of track_window_plan's form as contiguous int64, after
+    checking it against a recording of rec_len samples and windows of n:
+    ValueError unless every row has 0 <= count, 0 <= pad, pad + count <= n,
+    0 <= src and src + count <= rec_len."""
+    plan = np.ascontiguousarray(plan, np.int64)
+    if plan.ndim != 2 or plan.shape[1] != 3:
+        raise ValueError(f"window plan must be [n_windows, 3], got {plan.shape}")
+    src, count, pad = plan[:, 0], plan[:, 1], plan[:, 2]
+    # pad + count <= n and src + count <= rec_len, written so that no int64 sum can wrap
+    bad = (count < 0) | (count > n) | (pad < 0) | (pad > n - count) | (src < 0) | (src > rec_len - count)
+    if bad.any():
+        w = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"window {w}: (src, count, pad) = {tuple(int(v) for v in plan[w])} does not fit a window "
+                         f"of {n} samples in a recording of {rec_len}")
+    return plan
+
+
+def detect_tracks(frames, sr=SR, detector="host", dev_out=None):
     """predict.main (:735-740): cut the silent tail, detect signals, merge
     them into tracks -> (tracks, frames[:end], end seconds).  detector "host"
     runs identifytracks on numpy; "gpu" (or an acfe.tracks.SignalDetector to
     reuse) uploads the recording once and runs get_end and signal_noise on
     the device, the cut recording being a slice of that one buffer.  The
-    merging into tracks is host work on a few hundred boxes either way."""
+    merging into tracks is host work on a few hundred boxes either way.
+    A device detector appends that slice, the cut recording on the device,
+    to the list `dev_out` when one is given."""
     from identifytracks import get_end, get_tracks_from_signals, signal_noise
 
     if detector == "host":
@@ -156,6 +241,8 @@ def detect_tracks(frames, sr=SR, detector="host"):
     end = detector.get_end(dev)
     cut = int(sr * end)
     signals = detector.signal_noise(dev[:cut])[0] if cut else []
+    if dev_out is not None:
+        dev_out.append(dev[:cut])
     return get_tracks_from_signals(signals, end), frames[:cut], end
 
 
@@ -220,20 +307,48 @@ class Predictor:
             out.append(ops.sigmoid(self.model(self.frontend(x, pad_mode="constant"))))
         return torch.cat(out).float().cpu().numpy()
 
-    def predict_tracks(self, frames, threshold=None, batch_size=1024, rng=None, detector="host"):
+    @torch.no_grad()
+    def predict_plan(self, rec: torch.Tensor, plan: np.ndarray, batch_size=1024):
+        """predict_clips for windows that stay on the device: sigmoid outputs
+        [n_windows, classes] for the windows the table `plan`
+        (track_window_plan) cuts from the 1-D fp32 device recording `rec`,
+        cut and normalised by one kernel per chunk of batch_size windows."""
+        from acfe import frontend as fe
+        from acfe import ops
+
+        n = SR * 3
+        out = []
+        for a in range(0, len(plan), batch_size):
+            x = fe.normalize_windows(rec, plan[a:a + batch_size], n)
+            out.append(ops.sigmoid(self.model(self.frontend.features(x, pad_mode="constant"))))
+        return torch.cat(out).float().cpu().numpy()
+
+    def predict_tracks(self, frames, threshold=None, batch_size=1024, rng=None, detector="host", windows="host"):
         """Tracks of one recording with their ModelResult (predict.py:735-956);
-        `detector` as in detect_tracks ("gpu" keeps one SignalDetector per Predictor)."""
+        `detector` as in detect_tracks ("gpu" keeps one SignalDetector per Predictor).
+        windows "host" cuts every window with numpy and uploads them; "device"
+        computes only the window table on the host and cuts the windows out of
+        the device recording (the detector's buffer when detector is "gpu",
+        else one upload) -- the same windows, so the same predictions."""
+        if windows not in ("host", "device"):
+            raise ValueError(f"windows {windows!r}: expected 'host' or 'device'")
         if detector == "gpu":
             if self._detector is None:
                 from acfe.tracks import SignalDetector
 
                 self._detector = SignalDetector(device=self.device, sr=SR)
             detector = self._detector
-        tracks, frames, end = detect_tracks(np.asarray(frames, np.float32), detector=detector)
+        dev = []
+        tracks, frames, end = detect_tracks(np.asarray(frames, np.float32), detector=detector, dev_out=dev)
         thresh = self.meta.get("threshold", 0.7) if threshold is None else threshold
-        wins = track_windows(frames, SR, tracks, rng=rng)
-        counts = [len(w) for w in wins]
-        probs = self.predict_clips(np.concatenate(wins), batch_size) if sum(counts) else None
+        if windows == "host":
+            wins = track_windows(frames, SR, tracks, rng=rng)
+            counts = [len(w) for w in wins]
+            probs = self.predict_clips(np.concatenate(wins), batch_size) if sum(counts) else None
+        else:
+            plan, counts = track_window_plan(len(frames), SR, tracks, rng=rng)
+            rec = dev[0] if dev else torch.from_numpy(np.ascontiguousarray(frames)).to(self.device)
+            probs = self.predict_plan(rec, plan, batch_size) if len(plan) else None
         at = 0
         for t, c in zip(tracks, counts):
             if c == 0:
@@ -272,12 +387,16 @@ def main(argv=None):
     ap.add_argument("--mode", choices=("tracks", "windows"), default="tracks")
     ap.add_argument("--detector", choices=("host", "gpu"), default="host",
                     help="track detection (--mode tracks): numpy on the host, or the HIP kernels of acfe.tracks")
+    ap.add_argument("--windows", choices=("host", "device"), default="host",
+                    help="the 3 s windows of the tracks (--mode tracks): cut with numpy and uploaded, or cut and "
+                         "normalised on the GPU from the uploaded recording by the table of window positions")
     a = ap.parse_args(argv)
     p = Predictor(a.model)
     for f in a.file:
         t0 = time.perf_counter()
         if a.mode == "tracks":
-            tracks, end = p.predict_tracks(load_recording(f), a.threshold, a.batch_size, detector=a.detector)
+            tracks, end = p.predict_tracks(load_recording(f), a.threshold, a.batch_size, detector=a.detector,
+                                           windows=a.windows)
             r = {"file": str(f), "end": end, "tracks": [t.get_meta() for t in tracks]}
         else:
             r = p.predict_file(f, a.stride, a.batch_size, a.threshold)

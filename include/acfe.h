@@ -35,6 +35,7 @@
  *   acfe_morph_box         identifytracks.py:92,98-99  cv2 open / dilate / erode
  *   acfe_map_runs          identifytracks.py:104     connectedComponentsWithStats (runs; host union)
  *   acfe_chunk_flat        identifytracks.py:41-43   get_end's max == min chunk test
+ *   acfe_windows_normalize predict_utils.py:59-160   load_samples' window cut + normalize_data
  */
 #ifndef ACFE_H
 #define ACFE_H
@@ -620,6 +621,22 @@ int acfe_map_runs(const uint8_t* map, int rows, int cols, int* runs, int cap, in
  * max of img[:, c*chunk : (c+1)*chunk] equals its min, else 0, for c <
  * n_chunks (n_chunks * chunk <= cols). */
 int acfe_chunk_flat(const float* img, int rows, int cols, int chunk, int n_chunks, int* flags, void* stream);
+
+/* The classification windows of a device-resident recording, cut and
+ * normalised in one pass (predict_utils.py:59-150 + normalize_data).  plan is
+ * a device table [batch][3] of int64 {src, count, pad}: window b is the
+ * zero-padded vector v[i] = rec[src + i - pad] for pad <= i < pad + count and
+ * 0 elsewhere, i < n.  out[b][i] = ((v[i] - min v) / (max v - min v) + 1e-6
+ * - 0.5) * 2 in that float32 order, bit-identical to acfe_normalize_stats +
+ * acfe_normalize_apply on the materialised window (an empty window gives the
+ * same 0 / 0 NaNs); stats (may be NULL) receives {min v, max v - min v} per
+ * window.  The padding zeros take part in min / max whenever count < n.
+ * A valid row has 0 <= pad, 0 <= count, pad + count <= n, 0 <= src and
+ * src + count <= rec_len; whatever the table holds, nothing outside
+ * rec[0, rec_len) is read (such a sample counts as zero) and nothing outside
+ * out[b] is written. */
+int acfe_windows_normalize(const float* rec, int64_t rec_len, const int64_t* plan, int batch, int n, float* out,
+                           float* stats, void* stream);
 
 #ifdef __cplusplus
 }
