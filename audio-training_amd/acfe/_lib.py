@@ -75,6 +75,7 @@ SIGNATURES: dict[str, list] = {
     "acfe_stem_wgrad": [P, I32, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, P, F32, P, P],
     "acfe_stem_bwd_bn": [P, P, P, I32, I32, I32, I32, I32, I32, I32, P, P, P, P, I32, P, I32, P, F32, P, P, P],
     "acfe_reduce_blocks": [I64],
+    "acfe_nn_launch_info": [I32, I64, I32, I32, I32, P],
     "acfe_bn_stats": [P, I64, I32, I32, P, P],
     "acfe_bn_finalize": [P, I32, I32, I32, F64, P, P, F32, F32, P, P, I32, P, P, P, P, P],
     "acfe_bn_apply": [P, I32, I64, I32, P, P, I32, P, I32, P],
@@ -190,6 +191,27 @@ def wgrad_halo_info(N, H, W, C, K, fold=False, unpool=False):
     if not lib.acfe_conv2d_wgrad_halo_info(N, H, W, C, K, int(fold), int(unpool), out):
         return None
     return dict(zip(HALO_FIELDS, out))
+
+
+# ACFE_NN_* of include/acfe.h, in order
+NN_OPS = ("bn_stats", "bn_finalize", "bn_apply", "bn_bwd_reduce", "bn_bwd_finalize", "bn_bwd_apply",
+          "bn_bwd_apply_pool", "add", "add_stats", "relu_bwd", "relu_bwd_sum", "dropout", "cast", "channel_sum",
+          "channel_sum_finalize", "maxpool", "maxpool_bwd", "maxpool_fused", "maxpool_bwd_argmax",
+          "maxpool_bwd_argmax_bn", "avgpool", "avgpool_bwd", "axis_pool", "axis_pool_bwd", "dense_fwd", "dense_bwd",
+          "dense_bwd_w", "loss", "sigmoid", "adam")
+NN_FIELDS = ("variant", "grid", "block", "passes")
+NN_SCALAR, NN_VEC8, NN_SLAB = 0, 1, 2
+
+
+def nn_launch_info(op, rows, C=8, aligned=True, slab=False, geo=None):
+    """acfe_nn_launch_info as a dict of NN_FIELDS (the launch plan of a
+    csrc/nn.hip entry point, host only), or None where the launcher returns
+    ACFE_E_INVAL.  op: a name of NN_OPS; geo = (H, W, kh, kw) for the pools
+    (rows = N); conventions of rows / C per op in include/acfe.h."""
+    out = (I32 * 4)(*(geo or (0, 0, 0, 0)))
+    if lib.acfe_nn_launch_info(NN_OPS.index(op), rows, C, int(aligned), int(slab), out) != 1:
+        return None
+    return dict(zip(NN_FIELDS, out))
 
 
 def exported_symbols() -> list[str]:

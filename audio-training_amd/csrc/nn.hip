@@ -68,10 +68,12 @@ __device__ __forceinline__ void st8(float* p, const float* f) {
 }
 
 static bool al16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static bool vec_ok(long long n, int C, const void* a, const void* b = nullptr, const void* c = nullptr,
-                   const void* d = nullptr) {
-  return C % 8 == 0 && n % 8 == 0 && n / 8 < 0xFFFFFFFFll && al16(a) && al16(b) && al16(c) && al16(d);
+static bool all16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr,
+                  const void* e = nullptr) {
+  return al16(a) && al16(b) && al16(c) && al16(d) && al16(e);
 }
+// the shape half of the 8-wide test (the alignment half is all16 of the launcher's buffers)
+static bool vec_shape(long long n, int C) { return C % 8 == 0 && n % 8 == 0 && n / 8 < 0xFFFFFFFFll; }
 static int vgrid(long long nvec) { return grid_for(nvec, 256, 16384); }
 
 
@@ -154,6 +156,193 @@ __device__ __forceinline__ void stats8_flush(const double* a, const double* b, i
 
 static bool stats8_ok(int C) { return C % 8 == 0 && C / 8 <= 256 && 256 % (C / 8) == 0 && C <= 2048; }
 
+// ---------------------------------------------------------------- launch plans
+// Which kernel of an entry point runs and on what grid: the one place that
+// decides it.  Every launcher below asks nn_plan with the alignment of its own
+// buffers; acfe_nn_launch_info (acfe.h) answers from the same function.
+#define MAXPOOL_SHAPES(X) X(1, 2) X(2, 2) X(3, 3)
+static bool maxpool_shape(int kh, int kw) {
+#define MS(A, B) || (kh == A && kw == B)
+  return false MAXPOOL_SHAPES(MS);
+#undef MS
+}
+enum { NN_SCALAR = 0, NN_VEC8 = 1, NN_SLAB = 2 };
+struct NnPlan {
+  int variant, grid, block;
+  long long passes;
+};
+struct PoolGeo {
+  int H, W, kh, kw;
+};
+constexpr int ADAM_GRID_CAP = 4096, DENSE_W_GRID_CAP = 8192;
+// threads per workgroup of k_bn_bwd_apply8: with the channel-sum slab the grid
+// is fixed at acfe_reduce_blocks(rows) workgroups (<= 1024), so the block size
+// sets how many 16-B vectors are in flight per CU
+// (256: the REG path and stats8_flush assume each thread keeps the same 8
+// channels across its grid-stride loop, i.e. gridDim * 256 a multiple of
+// C / 8, which stats8_ok guarantees for this block size only)
+constexpr int BWD_APPLY_NT = 256;
+
+static int nn_plan(int op, long long rows, int C, bool aligned, bool slab, const PoolGeo* geo, NnPlan* out) {
+  NnPlan r{NN_SCALAR, 0, 256, 0};
+  const long long n = rows * C;
+  // grid-stride kernels: `items` work items (16-B vectors, windows or elements) over grid workgroups
+  auto strided = [&](int variant, long long items, int grid, int per_block = 256) {
+    r.variant = variant;
+    r.grid = grid;
+    r.passes = (items + (long long)grid * per_block - 1) / ((long long)grid * per_block);
+  };
+  auto flat = [&](long long ne) {  // elementwise over ne elements: 8-wide or scalar
+    if (ne < 0) return (int)ACFE_E_INVAL;
+    if (ne == 0) return 1;
+    if (vec_shape(ne, 8) && aligned) strided(NN_VEC8, ne / 8, vgrid(ne / 8));
+    else strided(NN_SCALAR, ne, grid_for(ne));
+    return 1;
+  };
+  int rc = 1;
+  switch (op) {
+    case ACFE_NN_BN_STATS:
+    case ACFE_NN_BN_BWD_REDUCE:
+    case ACFE_NN_CHANNEL_SUM: {
+      if (rows <= 0 || C <= 0 || C > 2048) return ACFE_E_INVAL;
+      r.variant = vec_shape(n, C) && aligned ? NN_VEC8 : NN_SCALAR;
+      r.grid = red_blocks(rows);
+      // a workgroup sums ceil(rows / grid) rows, 256 / tpr of them side by side
+      const int units = r.variant ? C / 8 : C, tpr = units < 256 ? units : 256, rpp = 256 / tpr;
+      const long long per = (rows + r.grid - 1) / r.grid;
+      r.passes = (per + rpp - 1) / rpp;
+      break;
+    }
+    case ACFE_NN_BN_FINALIZE:
+    case ACFE_NN_BN_BWD_FINALIZE:
+    case ACFE_NN_CHANNEL_SUM_FINALIZE:
+      if (rows <= 0 || C <= 0) return ACFE_E_INVAL;
+      r.block = SLAB_THREADS;
+      r.grid = cdiv(C, SLAB_CH);
+      r.passes = (rows + SLAB_RG - 1) / SLAB_RG;  // slab rows per thread
+      break;
+    case ACFE_NN_BN_APPLY:
+      if (rows < 0 || C <= 0) return ACFE_E_INVAL;
+      if (n == 0) break;
+      if (vec_shape(n, C) && aligned && C <= 4096) strided(NN_VEC8, n / 8, vgrid(n / 8));
+      else strided(NN_SCALAR, n, grid_for(n));
+      break;
+    case ACFE_NN_BN_BWD_APPLY:
+    case ACFE_NN_BN_BWD_APPLY_POOL: {
+      if (rows < 0 || C <= 0) return ACFE_E_INVAL;
+      if (n == 0) break;
+      const bool vec = vec_shape(n, C) && aligned && C <= 2048;
+      if (op == ACFE_NN_BN_BWD_APPLY_POOL && !vec) return ACFE_E_INVAL;
+      if (slab && (!vec || !stats8_ok(C))) return ACFE_E_INVAL;
+      r.block = vec ? BWD_APPLY_NT : 256;
+      if (vec) strided(slab ? NN_SLAB : NN_VEC8, n / 8, slab ? red_blocks(rows) : vgrid(n / 8), BWD_APPLY_NT);
+      else strided(NN_SCALAR, n, grid_for(n));
+      break;
+    }
+    case ACFE_NN_ADD:
+    case ACFE_NN_RELU_BWD:
+    case ACFE_NN_DROPOUT:
+    case ACFE_NN_CAST:
+      rc = flat(rows);
+      break;
+    case ACFE_NN_SIGMOID:
+    case ACFE_NN_ADAM:
+      if (rows < 0) return ACFE_E_INVAL;
+      if (rows > 0) strided(NN_SCALAR, rows, grid_for(rows, 256, op == ACFE_NN_ADAM ? ADAM_GRID_CAP : 8192));
+      break;
+    case ACFE_NN_ADD_STATS:
+    case ACFE_NN_RELU_BWD_SUM:
+      if (rows <= 0 || !stats8_ok(C) || !(vec_shape(n, C) && aligned)) return ACFE_E_INVAL;
+      strided(NN_SLAB, n / 8, red_blocks(rows));
+      break;
+    case ACFE_NN_MAXPOOL:
+    case ACFE_NN_MAXPOOL_BWD:
+    case ACFE_NN_MAXPOOL_FUSED:
+    case ACFE_NN_MAXPOOL_BWD_ARGMAX:
+    case ACFE_NN_MAXPOOL_BWD_ARGMAX_BN: {
+      if (!geo) return ACFE_E_INVAL;
+      const int N = (int)rows, H = geo->H, W = geo->W, kh = geo->kh, kw = geo->kw;
+      const bool plain = op == ACFE_NN_MAXPOOL || op == ACFE_NN_MAXPOOL_BWD;
+      if (rows < 0 || rows > 0x7fffffffll || kh <= 0 || kw <= 0 || (!plain && N <= 0)) return ACFE_E_INVAL;
+      if (op != ACFE_NN_MAXPOOL_BWD && (H < kh || W < kw)) return ACFE_E_INVAL;
+      const int P = H / kh, Q = W / kw;
+      const long long nin = (long long)N * H * W * C, nout = (long long)N * P * Q * C;
+      const long long nw = (long long)N * P * Q * (C / 8);  // (window, 8 channels) items
+      const bool vec0 = vec_shape(nin, C) && aligned && maxpool_shape(kh, kw), vec = vec0 && nw < 0xFFFFFFFFll;
+      if (op == ACFE_NN_MAXPOOL) {
+        if (nout == 0) break;
+        if (vec) strided(NN_VEC8, nw, vgrid(nout / 8));
+        else strided(NN_SCALAR, nout, grid_for(nout));
+      } else if (op == ACFE_NN_MAXPOOL_BWD) {
+        if (nin == 0) break;
+        if (vec && P > 0 && Q > 0) strided(NN_VEC8, nw, vgrid(nw));
+        else strided(NN_SCALAR, nin, grid_for(nin));
+      } else if (op == ACFE_NN_MAXPOOL_BWD_ARGMAX_BN) {
+        if (!vec0 || !stats8_ok(C) || (long long)N * P >= (1ll << 31)) return ACFE_E_INVAL;
+        // a workgroup per pooled row (n, p), two vectors of the row per thread and pass
+        r.variant = NN_SLAB;
+        r.grid = red_blocks((long long)N * H * W);
+        r.passes = (((long long)N * P + r.grid - 1) / r.grid) * (((long long)Q * (C / 8) + 511) / 512);
+      } else {
+        if (!vec || (slab && op == ACFE_NN_MAXPOOL_FUSED && !stats8_ok(C))) return ACFE_E_INVAL;
+        const bool sl = slab && op == ACFE_NN_MAXPOOL_FUSED;
+        strided(sl ? NN_SLAB : NN_VEC8, nw, sl ? red_blocks((long long)N * P * Q) : vgrid(nw));
+      }
+      break;
+    }
+    case ACFE_NN_AVGPOOL:
+    case ACFE_NN_AVGPOOL_BWD: {
+      if (!geo) return ACFE_E_INVAL;
+      const int N = (int)rows, H = geo->H, W = geo->W, k = geo->kh;
+      if (rows < 0 || rows > 0x7fffffffll || k <= 0) return ACFE_E_INVAL;
+      const int P = (H + k - 1) / k, Q = (W + k - 1) / k;
+      const long long nin = (long long)N * H * W * C, nout = (long long)N * P * Q * C;
+      const long long nw = (long long)N * P * Q * (C / 8);
+      const long long ne = op == ACFE_NN_AVGPOOL ? nout : nin;
+      if (ne == 0) break;
+      if (vec_shape(nin, C) && aligned && nw < 0xFFFFFFFFll) strided(NN_VEC8, nw, vgrid(nw));
+      else strided(NN_SCALAR, ne, grid_for(ne));
+      break;
+    }
+    case ACFE_NN_AXIS_POOL:
+    case ACFE_NN_AXIS_POOL_BWD:
+      if (rows < 0 || C <= 0) return ACFE_E_INVAL;
+      if (n > 0) strided(NN_SCALAR, n, grid_for(n));
+      break;
+    case ACFE_NN_DENSE_FWD:
+    case ACFE_NN_DENSE_BWD:
+      if (rows < 0 || C <= 0) return ACFE_E_INVAL;
+      if (n > 0) strided(NN_SCALAR, n, grid_for(n));
+      break;
+    case ACFE_NN_DENSE_BWD_W:
+      if (rows <= 1 || C <= 0) return ACFE_E_INVAL;
+      strided(NN_SCALAR, n, (int)std::min<long long>((n + 3) / 4, DENSE_W_GRID_CAP), 4);
+      break;
+    case ACFE_NN_LOSS:
+      if (rows <= 0 || rows > 0x7fffffffll || C <= 0) return ACFE_E_INVAL;
+      r.grid = (int)rows;
+      r.passes = (C + 255) / 256;
+      break;
+    default:
+      return ACFE_E_INVAL;
+  }
+  *out = r;
+  return rc;
+}
+
+ACFE_API int acfe_nn_launch_info(int op, long long rows, int C, int aligned, int slab, int* out) {
+  if (!out) return ACFE_E_INVAL;
+  const PoolGeo geo{out[0], out[1], out[2], out[3]};
+  NnPlan p;
+  const int rc = nn_plan(op, rows, C, aligned != 0, slab != 0, &geo, &p);
+  if (rc < 0) return rc;
+  out[0] = p.variant;
+  out[1] = p.grid;
+  out[2] = p.block;
+  out[3] = (int)std::min<long long>(p.passes, 0x7fffffffll);
+  return 1;
+}
+
 // ---------------------------------------------------------------- BN statistics
 // part[blk][2][C] = {sum x, sum x^2} over the block's rows (double)
 template <typename T>
@@ -235,9 +424,10 @@ __global__ void __launch_bounds__(256) k_bn_stats8(const T* __restrict__ x, long
 }
 
 ACFE_API int acfe_bn_stats(const void* x, long long rows, int C, int dtype, double* part, void* stream) {
-  if (!x || !part || rows <= 0 || C <= 0 || C > 2048) return ACFE_E_INVAL;
-  const int nb = red_blocks(rows);
-  if (vec_ok(rows * C, C, x)) {
+  NnPlan pl;
+  if (!x || !part || nn_plan(ACFE_NN_BN_STATS, rows, C, all16(x), false, nullptr, &pl) < 0) return ACFE_E_INVAL;
+  const int nb = pl.grid;
+  if (pl.variant == NN_VEC8) {
     DISPATCH1(dtype, T, hipLaunchKernelGGL(k_bn_stats8<T>, dim3(nb), dim3(256), 2 * C * sizeof(double),
                                            strm(stream), (const T*)x, rows, C, part));
   } else {
@@ -289,7 +479,9 @@ ACFE_API int acfe_bn_finalize(const double* part, int nrows, int ld, int C, doub
   if (!scale || !shift || C <= 0 || (training && (!part || nrows <= 0 || count <= 0)) ||
       (!training && (!moving_mean || !moving_var)))
     return ACFE_E_INVAL;
-  hipLaunchKernelGGL(k_bn_finalize, dim3(cdiv(C, SLAB_CH)), dim3(SLAB_THREADS), 0, strm(stream), part, nrows, ld, C, count,
+  NnPlan pl;
+  if (nn_plan(ACFE_NN_BN_FINALIZE, training ? nrows : 1, C, true, false, nullptr, &pl) < 0) return ACFE_E_INVAL;
+  hipLaunchKernelGGL(k_bn_finalize, dim3(pl.grid), dim3(pl.block), 0, strm(stream), part, nrows, ld, C, count,
                      gamma, beta, eps, momentum, moving_mean, moving_var, training, scale, shift, mean, invstd);
   return launch_rc("acfe_bn_finalize");
 }
@@ -363,16 +555,18 @@ __global__ void __launch_bounds__(256) k_bn_apply8(const TI* __restrict__ x, uns
 
 ACFE_API int acfe_bn_apply(const void* x, int x_dtype, long long rows, int C, const float* scale,
                            const float* shift, int relu, void* y, int y_dtype, void* stream) {
-  if (!x || !y || !scale || !shift || rows < 0 || C <= 0) return ACFE_E_INVAL;
+  NnPlan pl;
+  if (!x || !y || !scale || !shift || nn_plan(ACFE_NN_BN_APPLY, rows, C, all16(x, y), false, nullptr, &pl) < 0)
+    return ACFE_E_INVAL;
   const long long n = rows * C;
   if (n == 0) return ACFE_OK;
-  if (vec_ok(n, C, x, y) && C <= 4096) {
+  if (pl.variant == NN_VEC8) {
     DISPATCH1(x_dtype, TI, DISPATCH1(y_dtype, TO,
-        hipLaunchKernelGGL((k_bn_apply8<TI, TO>), dim3(vgrid(n / 8)), dim3(256), 2 * C * sizeof(float),
+        hipLaunchKernelGGL((k_bn_apply8<TI, TO>), dim3(pl.grid), dim3(256), 2 * C * sizeof(float),
                            strm(stream), (const TI*)x, (unsigned)(n / 8), C, scale, shift, relu, (TO*)y)));
   } else {
     DISPATCH1(x_dtype, TI, DISPATCH1(y_dtype, TO,
-        hipLaunchKernelGGL((k_bn_apply<TI, TO>), dim3(grid_for(n)), dim3(256), 0, strm(stream), (const TI*)x, n,
+        hipLaunchKernelGGL((k_bn_apply<TI, TO>), dim3(pl.grid), dim3(256), 0, strm(stream), (const TI*)x, n,
                            C, scale, shift, relu, (TO*)y)));
   }
   return launch_rc("acfe_bn_apply");
@@ -477,10 +671,12 @@ __global__ void __launch_bounds__(256) k_bn_bwd_reduce8(const TG* __restrict__ d
 ACFE_API int acfe_bn_bwd_reduce(const void* dy, int dy_dtype, const void* x, int x_dtype, long long rows, int C,
                                 const float* scale, const float* shift, const float* mean, const float* invstd,
                                 int relu, double* part, void* stream) {
-  if (!dy || !x || !scale || !shift || !mean || !invstd || !part || rows <= 0 || C <= 0 || C > 2048)
+  NnPlan pl;
+  if (!dy || !x || !scale || !shift || !mean || !invstd || !part ||
+      nn_plan(ACFE_NN_BN_BWD_REDUCE, rows, C, all16(dy, x), false, nullptr, &pl) < 0)
     return ACFE_E_INVAL;
-  const int nb = red_blocks(rows);
-  if (vec_ok(rows * C, C, dy, x)) {
+  const int nb = pl.grid;
+  if (pl.variant == NN_VEC8) {
     DISPATCH1(dy_dtype, TG, DISPATCH1(x_dtype, TX,
         hipLaunchKernelGGL((k_bn_bwd_reduce8<TG, TX>), dim3(nb), dim3(256), 2 * C * sizeof(double), strm(stream),
                            (const TG*)dy, (const TX*)x, rows, C, scale, shift, mean, invstd, relu, part)));
@@ -516,8 +712,11 @@ __global__ void __launch_bounds__(SLAB_THREADS) k_bn_bwd_finalize(const double* 
 ACFE_API int acfe_bn_bwd_finalize_ex(const double* part, int nrows, int C, double count, const float* scale,
                                      const float* mean, const float* invstd, float* dgamma, float* dbeta,
                                      float* coef, int accumulate, void* stream) {
-  if (!part || !scale || !mean || !invstd || !coef || nrows <= 0 || C <= 0) return ACFE_E_INVAL;
-  hipLaunchKernelGGL(k_bn_bwd_finalize, dim3(cdiv(C, SLAB_CH)), dim3(SLAB_THREADS), 0, strm(stream), part, nrows, C, count, scale,
+  NnPlan pl;
+  if (!part || !scale || !mean || !invstd || !coef ||
+      nn_plan(ACFE_NN_BN_BWD_FINALIZE, nrows, C, true, false, nullptr, &pl) < 0)
+    return ACFE_E_INVAL;
+  hipLaunchKernelGGL(k_bn_bwd_finalize, dim3(pl.grid), dim3(pl.block), 0, strm(stream), part, nrows, C, count, scale,
                      mean, invstd, dgamma, dbeta, coef, accumulate ? 1 : 0);
   return launch_rc("acfe_bn_bwd_finalize");
 }
@@ -557,13 +756,6 @@ struct PoolAdd {
   int H, W, k, P, Q, pt, pl, sub;
 };
 
-// threads per workgroup of k_bn_bwd_apply8: with the channel-sum slab the grid
-// is fixed at acfe_reduce_blocks(rows) workgroups (<= 1024), so the block size
-// sets how many 16-B vectors are in flight per CU
-// (256: the REG path and stats8_flush assume each thread keeps the same 8
-// channels across its grid-stride loop, i.e. gridDim * 256 a multiple of
-// C / 8, which stats8_ok guarantees for this block size only)
-constexpr int BWD_APPLY_NT = 256;
 template <typename TG, typename TX, typename TO, bool REG>
 __global__ void __launch_bounds__(BWD_APPLY_NT) k_bn_bwd_apply8(const TG* __restrict__ dy, const TX* __restrict__ x,
                                                        unsigned nvec, int C, const float* __restrict__ scale,
@@ -669,13 +861,16 @@ static int bn_bwd_apply_impl(const void* dy, int dy_dtype, const void* x, int x_
                              const float* scale, const float* shift, int relu, const float* coef, const void* add,
                              const Drop& d, void* dx, int dx_dtype, double* sum_part, void* stream,
                              PoolAdd pa = PoolAdd{nullptr, 0, 0, 0, 0, 0, 0, 0, 0}) {
-  if (!dy || !x || !scale || !shift || !coef || !dx || rows < 0 || C <= 0) return ACFE_E_INVAL;
+  if (!dy || !x || !scale || !shift || !coef || !dx) return ACFE_E_INVAL;
+  NnPlan pl;
+  if (nn_plan(pa.g ? ACFE_NN_BN_BWD_APPLY_POOL : ACFE_NN_BN_BWD_APPLY, rows, C, all16(dy, x, add, pa.g, dx),
+              sum_part != nullptr, nullptr, &pl) < 0)
+    return ACFE_E_INVAL;
   const long long n = rows * C;
   if (n == 0) return ACFE_OK;
-  if (pa.g && (!vec_ok(n, C, dy, x, pa.g, dx) || C > 2048 || add)) return ACFE_E_INVAL;
-  if (vec_ok(n, C, dy, x, add, dx) && C <= 2048) {
-    if (sum_part && !stats8_ok(C)) return ACFE_E_INVAL;
-    const int grid = sum_part ? red_blocks(rows) : vgrid(n / 8);
+  if (pa.g && add) return ACFE_E_INVAL;
+  if (pl.variant != NN_SCALAR) {
+    const int grid = pl.grid;
     const size_t shm = 5 * C * sizeof(float) + (sum_part ? 2 * C * sizeof(double) : 0);
     DISPATCH1(dy_dtype, TG, DISPATCH1(x_dtype, TX, DISPATCH1(dx_dtype, TO,
         if (sum_part) hipLaunchKernelGGL((k_bn_bwd_apply8<TG, TX, TO, true>), dim3(grid), dim3(BWD_APPLY_NT), shm,
@@ -685,9 +880,8 @@ static int bn_bwd_apply_impl(const void* dy, int dy_dtype, const void* x, int x_
                                 strm(stream), (const TG*)dy, (const TX*)x, (unsigned)(n / 8), C, scale, shift, relu,
                                 coef, (const TO*)add, d, (TO*)dx, sum_part, pa))));
   } else {
-    if (sum_part) return ACFE_E_INVAL;
     DISPATCH1(dy_dtype, TG, DISPATCH1(x_dtype, TX, DISPATCH1(dx_dtype, TO,
-        hipLaunchKernelGGL((k_bn_bwd_apply<TG, TX, TO>), dim3(grid_for(n)), dim3(256), 0, strm(stream),
+        hipLaunchKernelGGL((k_bn_bwd_apply<TG, TX, TO>), dim3(pl.grid), dim3(256), 0, strm(stream),
                            (const TG*)dy, (const TX*)x, n, C, scale, shift, relu, coef, (const TO*)add, d,
                            (TO*)dx))));
   }
@@ -788,13 +982,14 @@ __global__ void k_add8(const T* __restrict__ a, const T* __restrict__ b, unsigne
   }
 }
 ACFE_API int acfe_add(const void* a, const void* b, long long n, int relu, void* z, int dtype, void* stream) {
-  if (!a || !b || !z || n < 0) return ACFE_E_INVAL;
+  NnPlan pl;
+  if (!a || !b || !z || nn_plan(ACFE_NN_ADD, n, 8, all16(a, b, z), false, nullptr, &pl) < 0) return ACFE_E_INVAL;
   if (n == 0) return ACFE_OK;
-  if (vec_ok(n, 8, a, b, z))
-    DISPATCH1(dtype, T, hipLaunchKernelGGL(k_add8<T>, dim3(vgrid(n / 8)), dim3(256), 0, strm(stream), (const T*)a,
+  if (pl.variant == NN_VEC8)
+    DISPATCH1(dtype, T, hipLaunchKernelGGL(k_add8<T>, dim3(pl.grid), dim3(256), 0, strm(stream), (const T*)a,
                                            (const T*)b, (unsigned)(n / 8), relu, (T*)z));
   else
-    DISPATCH1(dtype, T, hipLaunchKernelGGL(k_add<T>, dim3(grid_for(n)), dim3(256), 0, strm(stream), (const T*)a,
+    DISPATCH1(dtype, T, hipLaunchKernelGGL(k_add<T>, dim3(pl.grid), dim3(256), 0, strm(stream), (const T*)a,
                                            (const T*)b, n, relu, (T*)z));
   return launch_rc("acfe_add");
 }
@@ -817,13 +1012,15 @@ __global__ void k_relu_bwd8(const T* __restrict__ dy, const T* __restrict__ y, u
   }
 }
 ACFE_API int acfe_relu_bwd(const void* dy, const void* y, long long n, void* dx, int dtype, void* stream) {
-  if (!dy || !y || !dx || n < 0) return ACFE_E_INVAL;
+  NnPlan pl;
+  if (!dy || !y || !dx || nn_plan(ACFE_NN_RELU_BWD, n, 8, all16(dy, y, dx), false, nullptr, &pl) < 0)
+    return ACFE_E_INVAL;
   if (n == 0) return ACFE_OK;
-  if (vec_ok(n, 8, dy, y, dx))
-    DISPATCH1(dtype, T, hipLaunchKernelGGL(k_relu_bwd8<T>, dim3(vgrid(n / 8)), dim3(256), 0, strm(stream),
+  if (pl.variant == NN_VEC8)
+    DISPATCH1(dtype, T, hipLaunchKernelGGL(k_relu_bwd8<T>, dim3(pl.grid), dim3(256), 0, strm(stream),
                                            (const T*)dy, (const T*)y, (unsigned)(n / 8), (T*)dx));
   else
-    DISPATCH1(dtype, T, hipLaunchKernelGGL(k_relu_bwd<T>, dim3(grid_for(n)), dim3(256), 0, strm(stream),
+    DISPATCH1(dtype, T, hipLaunchKernelGGL(k_relu_bwd<T>, dim3(pl.grid), dim3(256), 0, strm(stream),
                                            (const T*)dy, (const T*)y, n, (T*)dx));
   return launch_rc("acfe_relu_bwd");
 }
@@ -857,9 +1054,11 @@ __global__ void __launch_bounds__(256) k_relu_bwd8s(const T* __restrict__ dy, co
 }
 ACFE_API int acfe_relu_bwd_sum(const void* dy, const void* y, long long rows, int C, void* dx, int dtype,
                                double* partial, void* stream) {
-  if (!dy || !y || !dx || !partial || rows <= 0 || !stats8_ok(C) || !vec_ok(rows * C, C, dy, y, dx))
+  NnPlan pl;
+  if (!dy || !y || !dx || !partial ||
+      nn_plan(ACFE_NN_RELU_BWD_SUM, rows, C, all16(dy, y, dx), true, nullptr, &pl) < 0)
     return ACFE_E_INVAL;
-  DISPATCH1(dtype, T, hipLaunchKernelGGL(k_relu_bwd8s<T>, dim3(red_blocks(rows)), dim3(256), 2 * C * sizeof(double),
+  DISPATCH1(dtype, T, hipLaunchKernelGGL(k_relu_bwd8s<T>, dim3(pl.grid), dim3(256), 2 * C * sizeof(double),
                                          strm(stream), (const T*)dy, (const T*)y, (unsigned)(rows * C / 8), C, (T*)dx,
                                          partial));
   return launch_rc("acfe_relu_bwd_sum");
@@ -892,13 +1091,15 @@ __global__ void k_dropout8(const T* __restrict__ x, unsigned nvec, float rate, u
 }
 ACFE_API int acfe_dropout(const void* x, long long n, float rate, unsigned long long seed, void* y, int dtype,
                           void* stream) {
-  if (!x || !y || n < 0 || rate < 0.f || rate >= 1.f) return ACFE_E_INVAL;
+  NnPlan pl;
+  if (!x || !y || rate < 0.f || rate >= 1.f || nn_plan(ACFE_NN_DROPOUT, n, 8, all16(x, y), false, nullptr, &pl) < 0)
+    return ACFE_E_INVAL;
   if (n == 0) return ACFE_OK;
-  if (vec_ok(n, 8, x, y))
-    DISPATCH1(dtype, T, hipLaunchKernelGGL(k_dropout8<T>, dim3(vgrid(n / 8)), dim3(256), 0, strm(stream),
+  if (pl.variant == NN_VEC8)
+    DISPATCH1(dtype, T, hipLaunchKernelGGL(k_dropout8<T>, dim3(pl.grid), dim3(256), 0, strm(stream),
                                            (const T*)x, (unsigned)(n / 8), rate, seed, (T*)y));
   else
-    DISPATCH1(dtype, T, hipLaunchKernelGGL(k_dropout<T>, dim3(grid_for(n)), dim3(256), 0, strm(stream),
+    DISPATCH1(dtype, T, hipLaunchKernelGGL(k_dropout<T>, dim3(pl.grid), dim3(256), 0, strm(stream),
                                            (const T*)x, n, rate, seed, (T*)y));
   return launch_rc("acfe_dropout");
 }
@@ -1026,46 +1227,48 @@ __global__ void __launch_bounds__(256) k_maxpool_bwd8(const T* __restrict__ x, c
       }
   }
 }
-#define MAXPOOL_SHAPES(X) X(1, 2) X(2, 2) X(3, 3)
-
 ACFE_API int acfe_maxpool2d(const void* x, int N, int H, int W, int C, int kh, int kw, void* y, int dtype,
                             void* stream) {
-  if (!x || !y || N < 0 || kh <= 0 || kw <= 0 || H < kh || W < kw) return ACFE_E_INVAL;
+  const PoolGeo geo{H, W, kh, kw};
+  NnPlan pl;
+  if (!x || !y || nn_plan(ACFE_NN_MAXPOOL, N, C, all16(x, y), false, &geo, &pl) < 0) return ACFE_E_INVAL;
   const int P = H / kh, Q = W / kw;
   const long long n = (long long)N * P * Q * C;
   if (n == 0) return ACFE_OK;
-  if (vec_ok((long long)N * H * W * C, C, x, y) && (long long)N * P * Q * (C / 8) < 0xFFFFFFFFll) {
+  if (pl.variant == NN_VEC8) {
 #define MP(A, B)                                                                                             \
   if (kh == A && kw == B) {                                                                                  \
-    DISPATCH1(dtype, T, hipLaunchKernelGGL((k_maxpool8<T, A, B>), dim3(vgrid(n / 8)), dim3(256), 0,          \
+    DISPATCH1(dtype, T, hipLaunchKernelGGL((k_maxpool8<T, A, B>), dim3(pl.grid), dim3(256), 0,               \
                                            strm(stream), (const T*)x, N, H, W, C, P, Q, (T*)y));             \
     return launch_rc("acfe_maxpool2d");                                                                      \
   }
     MAXPOOL_SHAPES(MP)
 #undef MP
   }
-  DISPATCH1(dtype, T, hipLaunchKernelGGL(k_maxpool<T>, dim3(grid_for(n)), dim3(256), 0, strm(stream), (const T*)x,
+  DISPATCH1(dtype, T, hipLaunchKernelGGL(k_maxpool<T>, dim3(pl.grid), dim3(256), 0, strm(stream), (const T*)x,
                                          N, H, W, C, kh, kw, P, Q, (T*)y));
   return launch_rc("acfe_maxpool2d");
 }
 ACFE_API int acfe_maxpool2d_bwd(const void* x, const void* dy, int N, int H, int W, int C, int kh, int kw,
                                 void* dx, int dtype, void* stream) {
-  if (!x || !dy || !dx || N < 0 || kh <= 0 || kw <= 0) return ACFE_E_INVAL;
+  const PoolGeo geo{H, W, kh, kw};
+  NnPlan pl;
+  if (!x || !dy || !dx || nn_plan(ACFE_NN_MAXPOOL_BWD, N, C, all16(x, dy, dx), false, &geo, &pl) < 0)
+    return ACFE_E_INVAL;
   const int P = H / kh, Q = W / kw;
   const long long n = (long long)N * H * W * C;
   if (n == 0) return ACFE_OK;
-  if (vec_ok(n, C, x, dy, dx) && (long long)N * P * Q * (C / 8) < 0xFFFFFFFFll && P > 0 && Q > 0) {
-    const long long nw = (long long)N * P * Q * (C / 8);
+  if (pl.variant == NN_VEC8) {
 #define MPB(A, B)                                                                                           \
   if (kh == A && kw == B) {                                                                                 \
-    DISPATCH1(dtype, T, hipLaunchKernelGGL((k_maxpool_bwd8<T, A, B>), dim3(vgrid(nw)), dim3(256), 0,        \
+    DISPATCH1(dtype, T, hipLaunchKernelGGL((k_maxpool_bwd8<T, A, B>), dim3(pl.grid), dim3(256), 0,          \
                                            strm(stream), (const T*)x, (const T*)dy, N, H, W, C, P, Q, (T*)dx)); \
     return launch_rc("acfe_maxpool2d_bwd");                                                                 \
   }
     MAXPOOL_SHAPES(MPB)
 #undef MPB
   }
-  DISPATCH1(dtype, T, hipLaunchKernelGGL(k_maxpool_bwd<T>, dim3(grid_for(n)), dim3(256), 0, strm(stream),
+  DISPATCH1(dtype, T, hipLaunchKernelGGL(k_maxpool_bwd<T>, dim3(pl.grid), dim3(256), 0, strm(stream),
                                          (const T*)x, (const T*)dy, N, H, W, C, kh, kw, P, Q, (T*)dx));
   return launch_rc("acfe_maxpool2d_bwd");
 }
@@ -1294,15 +1497,15 @@ __global__ void __launch_bounds__(256) k_maxpool_bwd8i_bn(const uint8_t* __restr
 static int maxpool_fused_impl(const void* x, int N, int H, int W, int C, int kh, int kw, void* y, uint8_t* argmax,
                               float drop_rate, unsigned long long seed, double* stats_part, int dtype,
                               const float* bsc, const float* bsh, int brelu, void* stream) {
-  if (!x || !y || N <= 0 || kh <= 0 || kw <= 0 || H < kh || W < kw || drop_rate < 0.f || drop_rate >= 1.f)
+  const PoolGeo geo{H, W, kh, kw};
+  NnPlan pl;
+  if (!x || !y || drop_rate < 0.f || drop_rate >= 1.f || (!bsc != !bsh) ||
+      nn_plan(ACFE_NN_MAXPOOL_FUSED, N, C, all16(x, y) && !((uintptr_t)argmax & 7), stats_part != nullptr, &geo,
+              &pl) < 0)
     return ACFE_E_INVAL;
   const int P = H / kh, Q = W / kw;
-  const long long rows = (long long)N * P * Q;
-  if (!vec_ok((long long)N * H * W * C, C, x, y) || ((uintptr_t)argmax & 7) || rows * (C / 8) >= 0xFFFFFFFFll ||
-      (stats_part && !stats8_ok(C)) || (!bsc != !bsh))
-    return ACFE_E_INVAL;
   const Drop d = make_drop(drop_rate, seed);
-  const int grid = stats_part ? red_blocks(rows) : vgrid(rows * C / 8);
+  const int grid = pl.grid;
   const size_t shm = stats_part ? 2 * C * sizeof(double) : 0;
 #define MPF(A, B)                                                                                           \
   if (kh == A && kw == B) {                                                                                 \
@@ -1336,17 +1539,16 @@ ACFE_API int acfe_bn_maxpool2d_fused(const void* x, int N, int H, int W, int C, 
 ACFE_API int acfe_maxpool2d_bwd_argmax(const uint8_t* argmax, const void* dy, int N, int H, int W, int C, int kh,
                                        int kw, float drop_rate, unsigned long long seed, void* dx, int dtype,
                                        void* stream) {
-  if (!argmax || !dy || !dx || N <= 0 || kh <= 0 || kw <= 0 || H < kh || W < kw || drop_rate < 0.f ||
-      drop_rate >= 1.f)
+  const PoolGeo geo{H, W, kh, kw};
+  NnPlan pl;
+  if (!argmax || !dy || !dx || drop_rate < 0.f || drop_rate >= 1.f ||
+      nn_plan(ACFE_NN_MAXPOOL_BWD_ARGMAX, N, C, all16(dy, dx) && !((uintptr_t)argmax & 7), false, &geo, &pl) < 0)
     return ACFE_E_INVAL;
   const int P = H / kh, Q = W / kw;
-  const long long nw = (long long)N * P * Q * (C / 8);
-  if (!vec_ok((long long)N * H * W * C, C, dy, dx) || ((uintptr_t)argmax & 7) || nw >= 0xFFFFFFFFll)
-    return ACFE_E_INVAL;
   const Drop d = make_drop(drop_rate, seed);
 #define MPBI(A, B)                                                                                          \
   if (kh == A && kw == B) {                                                                                 \
-    DISPATCH1(dtype, T, hipLaunchKernelGGL((k_maxpool_bwd8i<T, A, B>), dim3(vgrid(nw)), dim3(256), 0,       \
+    DISPATCH1(dtype, T, hipLaunchKernelGGL((k_maxpool_bwd8i<T, A, B>), dim3(pl.grid), dim3(256), 0,         \
                                            strm(stream), argmax, (const T*)dy, N, H, W, C, P, Q, d, (T*)dx)); \
     return launch_rc("acfe_maxpool2d_bwd_argmax");                                                          \
   }
@@ -1362,13 +1564,13 @@ ACFE_API int acfe_maxpool2d_bwd_argmax_bn(const uint8_t* argmax, const void* dy,
                                           int kw, void* dx, int dtype, const void* x, const float* scale,
                                           const float* shift, const float* mean, const float* invstd, int relu,
                                           double* part, void* stream) {
-  if (!argmax || !dy || !dx || !x || !scale || !shift || !mean || !invstd || !part || N <= 0 || kh <= 0 ||
-      kw <= 0 || H < kh || W < kw || !stats8_ok(C))
+  const PoolGeo geo{H, W, kh, kw};
+  NnPlan pl;
+  if (!argmax || !dy || !dx || !x || !scale || !shift || !mean || !invstd || !part ||
+      nn_plan(ACFE_NN_MAXPOOL_BWD_ARGMAX_BN, N, C, all16(dy, dx, x) && !((uintptr_t)argmax & 7), true, &geo, &pl) < 0)
     return ACFE_E_INVAL;
   const int P = H / kh, Q = W / kw;
-  if (!vec_ok((long long)N * H * W * C, C, dy, dx, x) || ((uintptr_t)argmax & 7) || (long long)N * P >= (1ll << 31))
-    return ACFE_E_INVAL;
-  const int grid = red_blocks((long long)N * H * W);
+  const int grid = pl.grid;
 #define MPBB(A, B)                                                                                             \
   if (kh == A && kw == B) {                                                                                    \
     DISPATCH1(dtype, T, hipLaunchKernelGGL((k_maxpool_bwd8i_bn<T, A, B>), dim3(grid), dim3(256),               \
@@ -1411,8 +1613,10 @@ __global__ void __launch_bounds__(256) k_add8s(const T* __restrict__ a, const T*
 
 ACFE_API int acfe_add_stats(const void* a, const void* b, long long rows, int C, int relu, void* z, int dtype,
                             double* part, void* stream) {
-  if (!a || !b || !z || !part || rows <= 0 || !stats8_ok(C) || !vec_ok(rows * C, C, a, b, z)) return ACFE_E_INVAL;
-  DISPATCH1(dtype, T, hipLaunchKernelGGL(k_add8s<T>, dim3(red_blocks(rows)), dim3(256), 2 * C * sizeof(double),
+  NnPlan pl;
+  if (!a || !b || !z || !part || nn_plan(ACFE_NN_ADD_STATS, rows, C, all16(a, b, z), true, nullptr, &pl) < 0)
+    return ACFE_E_INVAL;
+  DISPATCH1(dtype, T, hipLaunchKernelGGL(k_add8s<T>, dim3(pl.grid), dim3(256), 2 * C * sizeof(double),
                                          strm(stream), (const T*)a, (const T*)b, (unsigned)(rows * C / 8), C, relu,
                                          (T*)z, part));
   return launch_rc("acfe_add_stats");
@@ -1465,7 +1669,9 @@ __global__ void k_avgpool_bwd(const T* __restrict__ dy, int N, int H, int W, int
           const int hh = p * k - pt + a, ww = q * k - pl + b;
           cnt += ((unsigned)hh < (unsigned)H && (unsigned)ww < (unsigned)W) ? 1 : 0;
         }
-      g = ld(dy, (((long long)n * P + p) * Q + q) * C + c) / (float)cnt;
+      // dy times the reciprocal of the count, as k_avgpool_bwd8 and the pool form of
+      // k_bn_bwd_apply8 store it (dy / cnt differs in the last bit for cnt 3, 6, 9)
+      g = ld(dy, (((long long)n * P + p) * Q + q) * C + c) * (1.0f / (float)cnt);
     }
     st(dx, i, g);
   }
@@ -1530,34 +1736,37 @@ __global__ void __launch_bounds__(256) k_avgpool_bwd8(const T* __restrict__ dy, 
 }
 
 ACFE_API int acfe_avgpool2d(const void* x, int N, int H, int W, int C, int k, void* y, int dtype, void* stream) {
-  if (!x || !y || N < 0 || k <= 0) return ACFE_E_INVAL;
+  const PoolGeo geo{H, W, k, k};
+  NnPlan plan;
+  if (!x || !y || nn_plan(ACFE_NN_AVGPOOL, N, C, all16(x, y), false, &geo, &plan) < 0) return ACFE_E_INVAL;
   const int P = (H + k - 1) / k, Q = (W + k - 1) / k;
   const int pt = ((P - 1) * k + k - H) / 2, pl = ((Q - 1) * k + k - W) / 2;
   const long long n = (long long)N * P * Q * C;
   if (n == 0) return ACFE_OK;
-  if (vec_ok((long long)N * H * W * C, C, x, y) && n / 8 < 0xFFFFFFFFll) {
-    DISPATCH1(dtype, T, hipLaunchKernelGGL(k_avgpool8<T>, dim3(vgrid(n / 8)), dim3(256), 0, strm(stream),
+  if (plan.variant == NN_VEC8) {
+    DISPATCH1(dtype, T, hipLaunchKernelGGL(k_avgpool8<T>, dim3(plan.grid), dim3(256), 0, strm(stream),
                                            (const T*)x, N, H, W, C, k, P, Q, pt, pl, (T*)y));
     return launch_rc("acfe_avgpool2d");
   }
-  DISPATCH1(dtype, T, hipLaunchKernelGGL(k_avgpool<T>, dim3(grid_for(n)), dim3(256), 0, strm(stream), (const T*)x,
+  DISPATCH1(dtype, T, hipLaunchKernelGGL(k_avgpool<T>, dim3(plan.grid), dim3(256), 0, strm(stream), (const T*)x,
                                          N, H, W, C, k, P, Q, pt, pl, (T*)y));
   return launch_rc("acfe_avgpool2d");
 }
 ACFE_API int acfe_avgpool2d_bwd(const void* dy, int N, int H, int W, int C, int k, void* dx, int dtype,
                                 void* stream) {
-  if (!dy || !dx || N < 0 || k <= 0) return ACFE_E_INVAL;
+  const PoolGeo geo{H, W, k, k};
+  NnPlan plan;
+  if (!dy || !dx || nn_plan(ACFE_NN_AVGPOOL_BWD, N, C, all16(dy, dx), false, &geo, &plan) < 0) return ACFE_E_INVAL;
   const int P = (H + k - 1) / k, Q = (W + k - 1) / k;
   const int pt = ((P - 1) * k + k - H) / 2, pl = ((Q - 1) * k + k - W) / 2;
   const long long n = (long long)N * H * W * C;
   if (n == 0) return ACFE_OK;
-  const long long nw = (long long)N * P * Q * (C / 8);
-  if (vec_ok(n, C, dy, dx) && nw < 0xFFFFFFFFll) {
-    DISPATCH1(dtype, T, hipLaunchKernelGGL(k_avgpool_bwd8<T>, dim3(vgrid(nw)), dim3(256), 0, strm(stream),
+  if (plan.variant == NN_VEC8) {
+    DISPATCH1(dtype, T, hipLaunchKernelGGL(k_avgpool_bwd8<T>, dim3(plan.grid), dim3(256), 0, strm(stream),
                                            (const T*)dy, N, H, W, C, k, P, Q, pt, pl, (T*)dx));
     return launch_rc("acfe_avgpool2d_bwd");
   }
-  DISPATCH1(dtype, T, hipLaunchKernelGGL(k_avgpool_bwd<T>, dim3(grid_for(n)), dim3(256), 0, strm(stream),
+  DISPATCH1(dtype, T, hipLaunchKernelGGL(k_avgpool_bwd<T>, dim3(plan.grid), dim3(256), 0, strm(stream),
                                          (const T*)dy, N, H, W, C, k, P, Q, pt, pl, (T*)dx));
   return launch_rc("acfe_avgpool2d_bwd");
 }
@@ -1623,19 +1832,24 @@ __global__ void k_axis_pool_bwd(const T* __restrict__ x, const float* __restrict
 }
 ACFE_API int acfe_axis_pool(const void* x, int x_dtype, long long outer, int L, int inner, float sharpness,
                             int mode, float* y, void* stream) {
-  if (!x || !y || outer < 0 || L <= 0 || inner <= 0 || (mode == 0 && sharpness == 0.f)) return ACFE_E_INVAL;
+  NnPlan pl;
+  if (!x || !y || L <= 0 || (mode == 0 && sharpness == 0.f) ||
+      nn_plan(ACFE_NN_AXIS_POOL, outer, inner, true, false, nullptr, &pl) < 0)
+    return ACFE_E_INVAL;
   const long long n = outer * inner;
   if (n == 0) return ACFE_OK;
-  DISPATCH1(x_dtype, T, hipLaunchKernelGGL(k_axis_pool<T>, dim3(grid_for(n)), dim3(256), 0, strm(stream),
+  DISPATCH1(x_dtype, T, hipLaunchKernelGGL(k_axis_pool<T>, dim3(pl.grid), dim3(256), 0, strm(stream),
                                            (const T*)x, outer, L, inner, sharpness, mode, y));
   return launch_rc("acfe_axis_pool");
 }
 ACFE_API int acfe_axis_pool_bwd(const void* x, int x_dtype, const float* dy, long long outer, int L, int inner,
                                 float sharpness, int mode, void* dx, void* stream) {
-  if (!x || !dy || !dx || outer < 0 || L <= 0 || inner <= 0) return ACFE_E_INVAL;
+  NnPlan pl;
+  if (!x || !dy || !dx || L <= 0 || nn_plan(ACFE_NN_AXIS_POOL_BWD, outer, inner, true, false, nullptr, &pl) < 0)
+    return ACFE_E_INVAL;
   const long long n = outer * inner;
   if (n == 0) return ACFE_OK;
-  DISPATCH1(x_dtype, T, hipLaunchKernelGGL(k_axis_pool_bwd<T>, dim3(grid_for(n)), dim3(256), 0, strm(stream),
+  DISPATCH1(x_dtype, T, hipLaunchKernelGGL(k_axis_pool_bwd<T>, dim3(pl.grid), dim3(256), 0, strm(stream),
                                            (const T*)x, dy, outer, L, inner, sharpness, mode, (T*)dx));
   return launch_rc("acfe_axis_pool_bwd");
 }
@@ -1653,9 +1867,10 @@ __global__ void k_dense(const float* __restrict__ x, const float* __restrict__ w
 }
 ACFE_API int acfe_dense_fwd(const float* x, const float* w, const float* bias, int B, int I, int O, float* z,
                             void* stream) {
-  if (!x || !w || !z || B < 0 || I <= 0 || O <= 0) return ACFE_E_INVAL;
+  NnPlan pl;
+  if (!x || !w || !z || I <= 0 || nn_plan(ACFE_NN_DENSE_FWD, B, O, true, false, nullptr, &pl) < 0) return ACFE_E_INVAL;
   if (B == 0) return ACFE_OK;
-  hipLaunchKernelGGL(k_dense, dim3(grid_for((long long)B * O)), dim3(256), 0, strm(stream), x, w, bias, B, I, O, z);
+  hipLaunchKernelGGL(k_dense, dim3(pl.grid), dim3(256), 0, strm(stream), x, w, bias, B, I, O, z);
   return launch_rc("acfe_dense_fwd");
 }
 // dx = dz w^T ; dw = x^T dz ; db = sum_b dz   (dw/db overwritten)
@@ -1693,12 +1908,13 @@ __global__ void __launch_bounds__(256) k_dense_bwd_w(const float* __restrict__ x
 }
 ACFE_API int acfe_dense_bwd(const float* x, const float* w, const float* dz, int B, int I, int O, float* dx,
                             float* dw, float* db, void* stream) {
-  if (!x || !w || !dz || !dw || B < 0 || I <= 0 || O <= 0) return ACFE_E_INVAL;
+  NnPlan px, pw;  // dx: a thread per element; dw, db: one wave per output
+  if (!x || !w || !dz || !dw || O <= 0 || nn_plan(ACFE_NN_DENSE_BWD, B, I, true, false, nullptr, &px) < 0 ||
+      nn_plan(ACFE_NN_DENSE_BWD_W, (long long)I + 1, O, true, false, nullptr, &pw) < 0)
+    return ACFE_E_INVAL;
   if (dx && B > 0)
-    hipLaunchKernelGGL(k_dense_bwd_x, dim3(grid_for((long long)B * I)), dim3(256), 0, strm(stream), dz, w, B, I, O,
-                       dx);
-  const long long nw = (long long)(I + 1) * O;  // one wave per output
-  hipLaunchKernelGGL(k_dense_bwd_w, dim3((unsigned)std::min<long long>((nw + 3) / 4, 8192)), dim3(256), 0,
+    hipLaunchKernelGGL(k_dense_bwd_x, dim3(px.grid), dim3(256), 0, strm(stream), dz, w, B, I, O, dx);
+  hipLaunchKernelGGL(k_dense_bwd_w, dim3(pw.grid), dim3(256), 0,
                      strm(stream), x, dz, B, I, O, dw, db);
   return launch_rc("acfe_dense_bwd");
 }
@@ -1782,9 +1998,11 @@ __global__ void k_mean(const float* __restrict__ v, int n, float* __restrict__ o
 // workspace: float[B]; grad_scale multiplies dz (e.g. 1/B for a batch mean)
 ACFE_API int acfe_loss(const float* z, const float* y, int B, int L, int mode, float grad_scale, float* loss,
                        float* dz, float* workspace, void* stream) {
-  if (!z || !y || !loss || !dz || !workspace || B <= 0 || L <= 0 || (mode != 0 && mode != 1))
+  NnPlan pl;
+  if (!z || !y || !loss || !dz || !workspace || (mode != 0 && mode != 1) ||
+      nn_plan(ACFE_NN_LOSS, B, L, true, false, nullptr, &pl) < 0)
     return ACFE_E_INVAL;
-  hipLaunchKernelGGL(k_loss, dim3(B), dim3(256), 0, strm(stream), z, y, B, L, mode, grad_scale, workspace, dz);
+  hipLaunchKernelGGL(k_loss, dim3(pl.grid), dim3(256), 0, strm(stream), z, y, B, L, mode, grad_scale, workspace, dz);
   int rc = launch_rc("acfe_loss");
   if (rc) return rc;
   hipLaunchKernelGGL(k_mean, dim3(1), dim3(256), 0, strm(stream), workspace, B, loss);
@@ -1796,9 +2014,10 @@ __global__ void k_sigmoid(const float* __restrict__ z, long long n, float* __res
     p[i] = 1.f / (1.f + expf(-z[i]));
 }
 ACFE_API int acfe_sigmoid(const float* z, long long n, float* p, void* stream) {
-  if (!z || !p || n < 0) return ACFE_E_INVAL;
+  NnPlan pl;
+  if (!z || !p || nn_plan(ACFE_NN_SIGMOID, n, 1, true, false, nullptr, &pl) < 0) return ACFE_E_INVAL;
   if (n == 0) return ACFE_OK;
-  hipLaunchKernelGGL(k_sigmoid, dim3(grid_for(n)), dim3(256), 0, strm(stream), z, n, p);
+  hipLaunchKernelGGL(k_sigmoid, dim3(pl.grid), dim3(256), 0, strm(stream), z, n, p);
   return launch_rc("acfe_sigmoid");
 }
 
@@ -1821,9 +2040,11 @@ __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float
 }
 ACFE_API int acfe_adam_step(float* params, const float* grads, float* m, float* v, long long n, float grad_scale,
                             float beta1, float beta2, float eps, float alpha, void* stream) {
-  if (!params || !grads || !m || !v || n < 0) return ACFE_E_INVAL;
+  NnPlan pl;
+  if (!params || !grads || !m || !v || nn_plan(ACFE_NN_ADAM, n, 1, true, false, nullptr, &pl) < 0)
+    return ACFE_E_INVAL;
   if (n == 0) return ACFE_OK;
-  hipLaunchKernelGGL(k_adam, dim3(grid_for(n, 256, 4096)), dim3(256), 0, strm(stream), params, grads, m, v, n,
+  hipLaunchKernelGGL(k_adam, dim3(pl.grid), dim3(256), 0, strm(stream), params, grads, m, v, n,
                      grad_scale, beta1, beta2, eps, alpha);
   return launch_rc("acfe_adam_step");
 }
@@ -1843,16 +2064,17 @@ __global__ void k_cast8(const TI* __restrict__ x, unsigned nvec, TO* __restrict_
   }
 }
 ACFE_API int acfe_cast(const void* x, int x_dtype, long long n, void* y, int y_dtype, void* stream) {
-  if (!x || !y || n < 0) return ACFE_E_INVAL;
+  NnPlan pl;
+  if (!x || !y || nn_plan(ACFE_NN_CAST, n, 8, all16(x, y), false, nullptr, &pl) < 0) return ACFE_E_INVAL;
   if (n == 0) return ACFE_OK;
-  if (vec_ok(n, 8, x, y)) {
+  if (pl.variant == NN_VEC8) {
     DISPATCH1(x_dtype, TI, DISPATCH1(y_dtype, TO,
-        hipLaunchKernelGGL((k_cast8<TI, TO>), dim3(vgrid(n / 8)), dim3(256), 0, strm(stream), (const TI*)x,
+        hipLaunchKernelGGL((k_cast8<TI, TO>), dim3(pl.grid), dim3(256), 0, strm(stream), (const TI*)x,
                            (unsigned)(n / 8), (TO*)y)));
     return launch_rc("acfe_cast");
   }
   DISPATCH1(x_dtype, TI, DISPATCH1(y_dtype, TO,
-      hipLaunchKernelGGL((k_cast<TI, TO>), dim3(grid_for(n)), dim3(256), 0, strm(stream), (const TI*)x, n,
+      hipLaunchKernelGGL((k_cast<TI, TO>), dim3(pl.grid), dim3(256), 0, strm(stream), (const TI*)x, n,
                          (TO*)y)));
   return launch_rc("acfe_cast");
 }
@@ -1868,8 +2090,10 @@ __global__ void __launch_bounds__(SLAB_THREADS) k_chan_sum_fin(const double* __r
 }
 // out[c] = beta*out[c] + sum of a slab's first row set (part [nrows][2][C]).
 ACFE_API int acfe_channel_sum_finalize(const double* part, int nrows, int C, float beta, float* out, void* stream) {
-  if (!part || !out || nrows <= 0 || C <= 0) return ACFE_E_INVAL;
-  hipLaunchKernelGGL(k_chan_sum_fin, dim3(cdiv(C, SLAB_CH)), dim3(SLAB_THREADS), 0, strm(stream), part, nrows, C, beta, out);
+  NnPlan pl;
+  if (!part || !out || nn_plan(ACFE_NN_CHANNEL_SUM_FINALIZE, nrows, C, true, false, nullptr, &pl) < 0)
+    return ACFE_E_INVAL;
+  hipLaunchKernelGGL(k_chan_sum_fin, dim3(pl.grid), dim3(pl.block), 0, strm(stream), part, nrows, C, beta, out);
   return launch_rc("acfe_channel_sum_finalize");
 }
 ACFE_API int acfe_channel_sum(const void* x, long long rows, int C, int dtype, double* part, float* out,
@@ -1878,7 +2102,10 @@ ACFE_API int acfe_channel_sum(const void* x, long long rows, int C, int dtype, d
   if (rows == 0) return hip_rc(hipMemsetAsync(out, 0, sizeof(float) * C, strm(stream)), "acfe_channel_sum");
   int rc = acfe_bn_stats(x, rows, C, dtype, part, stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_chan_sum_fin, dim3(cdiv(C, SLAB_CH)), dim3(SLAB_THREADS), 0, strm(stream), part, red_blocks(rows), C, beta,
-                     out);
+  NnPlan ps, pl;  // the slab rows acfe_bn_stats just wrote, then their sum
+  if (nn_plan(ACFE_NN_CHANNEL_SUM, rows, C, all16(x), false, nullptr, &ps) < 0 ||
+      nn_plan(ACFE_NN_CHANNEL_SUM_FINALIZE, ps.grid, C, true, false, nullptr, &pl) < 0)
+    return ACFE_E_INVAL;
+  hipLaunchKernelGGL(k_chan_sum_fin, dim3(pl.grid), dim3(pl.block), 0, strm(stream), part, ps.grid, C, beta, out);
   return launch_rc("acfe_channel_sum");
 }

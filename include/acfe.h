@@ -571,6 +571,67 @@ int acfe_loss(const float* z, const float* y, int B, int L, int mode, float grad
 int acfe_adam_step(float* params, const float* grads, float* m, float* v, long long n, float grad_scale,
                    float beta1, float beta2, float eps, float alpha, void* stream);
 
+/* Launch plan of the layer kernels above (csrc/nn.hip), host only: which of an
+ * entry point's kernels runs for a shape, and on what grid.  The launchers take
+ * their choice from the same function, so the answer is the launch.
+ *   op       one ACFE_NN_* below.
+ *   rows, C  the tensor is [rows][C].  Flat operations (ADD, RELU_BWD, DROPOUT,
+ *            CAST, SIGMOID, ADAM): rows = n elements, C is ignored (their 8-wide
+ *            test is n % 8 == 0).  Pools: rows = N clips and the geometry comes
+ *            in out[0..3] = {H, W, kh, kw} on entry (average pools: kh = k, kw
+ *            ignored).  BN_FINALIZE / BN_BWD_FINALIZE / CHANNEL_SUM_FINALIZE:
+ *            rows = the slab's nrows.  BN_BWD_APPLY covers acfe_bn_bwd_apply,
+ *            _dropout and _ex; BN_BWD_APPLY_POOL covers _pool and _sub with
+ *            rows = N H W.  MAXPOOL_FUSED covers acfe_bn_maxpool2d_fused too;
+ *            CHANNEL_SUM is the acfe_bn_stats launch of acfe_channel_sum.
+ *            AXIS_POOL(_BWD): rows = outer, C = inner.  DENSE_FWD: rows = B,
+ *            C = O.  DENSE_BWD: the dx kernel, rows = B, C = I.  DENSE_BWD_W: the
+ *            dw / db kernel (one wave per output, four per workgroup), rows =
+ *            I + 1, C = O.  LOSS: rows = B (one workgroup per row), C = L.
+ *   aligned  1 when every buffer the launcher tests is 16-B aligned (and the
+ *            argmax bytes 8-B aligned).
+ *   slab     1 when the statistics / channel-sum slab is requested (ignored by
+ *            the operations that always or never write one).
+ * out[4] = {variant (0 scalar, 1 eight-wide, 2 eight-wide on the slab grid
+ * acfe_reduce_blocks(rows)), grid (workgroups; 0: nothing is launched), block
+ * (threads), passes (loop iterations of the busiest thread: ceil(work items /
+ * (grid * block)) for the grid-stride kernels; for the row-partitioned
+ * reductions BN_STATS / BN_BWD_REDUCE / CHANNEL_SUM the rows one thread sums
+ * per channel group, whose f32 partial sums are flushed into doubles every 64
+ * (eight-wide) or 256 (scalar) of them)}.
+ * Returns 1, or ACFE_E_INVAL where the launcher would return that for the shape. */
+#define ACFE_NN_BN_STATS 0
+#define ACFE_NN_BN_FINALIZE 1
+#define ACFE_NN_BN_APPLY 2
+#define ACFE_NN_BN_BWD_REDUCE 3
+#define ACFE_NN_BN_BWD_FINALIZE 4
+#define ACFE_NN_BN_BWD_APPLY 5
+#define ACFE_NN_BN_BWD_APPLY_POOL 6
+#define ACFE_NN_ADD 7
+#define ACFE_NN_ADD_STATS 8
+#define ACFE_NN_RELU_BWD 9
+#define ACFE_NN_RELU_BWD_SUM 10
+#define ACFE_NN_DROPOUT 11
+#define ACFE_NN_CAST 12
+#define ACFE_NN_CHANNEL_SUM 13
+#define ACFE_NN_CHANNEL_SUM_FINALIZE 14
+#define ACFE_NN_MAXPOOL 15
+#define ACFE_NN_MAXPOOL_BWD 16
+#define ACFE_NN_MAXPOOL_FUSED 17
+#define ACFE_NN_MAXPOOL_BWD_ARGMAX 18
+#define ACFE_NN_MAXPOOL_BWD_ARGMAX_BN 19
+#define ACFE_NN_AVGPOOL 20
+#define ACFE_NN_AVGPOOL_BWD 21
+#define ACFE_NN_AXIS_POOL 22
+#define ACFE_NN_AXIS_POOL_BWD 23
+#define ACFE_NN_DENSE_FWD 24
+#define ACFE_NN_DENSE_BWD 25
+#define ACFE_NN_DENSE_BWD_W 26
+#define ACFE_NN_LOSS 27
+#define ACFE_NN_SIGMOID 28
+#define ACFE_NN_ADAM 29
+int acfe_nn_launch_info(int op, long long rows, int C, int aligned, int slab, int* out);
+
 /* ---- Track detection of the predict path (csrc/tracks.hip): the device form
  * of identifytracks.get_end (identifytracks.py:21-48) and signal_noise
  * (:51-143).  Images are row-major [rows][cols] = [frequency bin][frame] and
