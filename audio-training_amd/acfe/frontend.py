@@ -178,6 +178,50 @@ def normalize_windows(rec: torch.Tensor, plan, n: int, out: torch.Tensor | None 
     return out
 
 
+def sosfilt_segments(rec: torch.Tensor, seg, sos, out: torch.Tensor | None = None) -> torch.Tensor:
+    """scipy.signal.sosfilt of segments of the 1-D fp32 device recording
+    `rec`, each with its own filter, as one packed float32 device buffer:
+    out[dst + i] = float32(sosfilt(sos[k], float64(rec[src : src + len]))[i])
+    for the rows (src, len, dst) of the host table `seg` [n_seg, 3] and the
+    float64 second-order sections `sos` [n_seg, 2, 6]
+    (predict.sos_segment_plan; two identity sections copy the segment bit for
+    bit).  Computed in float64 by the chunked scan of csrc/sosfilt.hip, from a
+    zero state at each segment's first sample.  Both tables are validated on
+    the host (predict.check_sos_segments) before they are uploaded.  `out`
+    defaults to a new buffer of max(dst + len) rounded up to 4 floats;
+    elements of it that no segment covers are left as they were."""
+    from predict import check_sos_segments  # host-only index arithmetic, next to sos_segment_plan
+
+    require_cuda(rec, out)
+    if rec.dtype != torch.float32 or rec.dim() != 1 or not rec.is_contiguous():
+        raise TypeError("the recording must be a contiguous 1-D float32 tensor")
+    if out is not None and (out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise ValueError("bad out tensor")
+    seg = np.ascontiguousarray(seg, np.int64)
+    if seg.ndim != 2 or seg.shape[1] != 3:
+        raise ValueError(f"segment table must be [n_seg, 3], got {seg.shape}")
+    if out is not None:
+        out_len = out.numel()
+    elif len(seg):  # clipped so that a bad row reaches check_sos_segments' message, not an overflow here
+        out_len = int((np.clip(seg[:, 1], 0, 2**40) + np.clip(seg[:, 2], 0, 2**40)).max() + 3) & ~3
+    else:
+        out_len = 0
+    seg, sos = check_sos_segments(seg, sos, rec.numel(), out_len)
+    if out is None:
+        out = torch.empty(out_len, dtype=torch.float32, device=rec.device)
+    n_seg = seg.shape[0]
+    if n_seg == 0 or out_len == 0:
+        return out
+    nbytes = lib.acfe_sosfilt_workspace(out_len, n_seg)
+    _lib.check(nbytes, "acfe_sosfilt_workspace")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=rec.device)
+    dseg = torch.from_numpy(seg).to(rec.device)
+    dsos = torch.from_numpy(sos).to(rec.device)
+    call("acfe_sosfilt_segments", ptr(rec), rec.numel(), ptr(dseg), ptr(dsos), n_seg, ptr(out), out_len, ptr(ws),
+         stream())
+    return out
+
+
 def mix_up(x1, x2, lam, stats1=None, stats2=None) -> torch.Tensor:
     """tfdataset.mix_up image blend (tfdataset.py:950); lam [B] fp32 on device."""
     require_cuda(x1, x2, lam, stats1, stats2)

@@ -3,7 +3,7 @@
 predict_utils.py:9-239).
 
   python predict.py --file REC.wav CHECKPOINT_DIR [--stride 1] [--batch-size 1024] [--detector gpu]
-                    [--windows device]
+                    [--windows device] [--filter-freqs | --filter-below HZ]
 
 The recording is decoded on the host (WAV via scipy; the reference's ffmpeg /
 librosa loader is out of scope) and resampled to 48 kHz.
@@ -28,6 +28,15 @@ uploaded recording -- with --detector gpu the buffer the detector already
 holds -- so no window passes through host memory; the predictions are those
 of --windows host, which stays the default.
 
+--filter-freqs runs every track's audio through a second-order Butterworth
+band-pass at the track's own [freq_start, freq_end] before its windows are cut
+(predict_utils.load_samples:103-113, butter_bandpass :245-262);
+--filter-below HZ does so only for tracks with freq_end < HZ.  With --windows
+host this is scipy's sosfilt on the host; with --windows device the filter is
+the float64 HIP scan of acfe_sosfilt_segments, which writes the filtered tracks
+into one packed device buffer that the window kernel then reads, so the audio
+still never passes through host memory.  Both are off by default.
+
 --mode windows: the recording is uploaded once and 3 s windows every
 `stride` seconds are read in place by the fused front-end kernel; the
 per-recording result is the mean of the window probabilities.
@@ -39,6 +48,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import logging
 import math
 import sys
 import time
@@ -86,12 +96,66 @@ class ModelResult:
         return meta
 
 
+def butter_bandpass(lowcut, highcut, fs, order=2):
+    """The Butterworth filter of one track as float64 second-order sections
+    [n_sections, 6], or None for no filter.  For arguments scipy.signal.butter
+    accepts this is predict_utils.butter_bandpass (:245-256): lowcut > 0 gives
+    a "bandpass" [lowcut, highcut] (2 sections for order 2), otherwise a
+    "lowpass" at highcut (1 section).  Signal.extend can push a track's
+    freq_end past Nyquist, where that function raises inside scipy; those
+    inputs follow the reference's other copy (audiodataset.py:1347-1377):
+    highcut >= fs / 2 (or None) with a usable lowcut gives a "highpass" at
+    lowcut (1 section); no usable edge (neither 0 < lowcut < fs / 2 nor
+    0 < highcut < fs / 2), or highcut <= lowcut, gives None and the track is
+    left unfiltered.  Each departure from the plain band-pass / low-pass logs
+    one line."""
+    from scipy.signal import butter
+
+    nyq = 0.5 * fs
+    low = lowcut if lowcut is not None and 0 < lowcut < nyq else None
+    if highcut is not None and highcut <= (lowcut or 0):
+        logging.warning("No freq to filter: band [%s, %s]", lowcut, highcut)
+        return None
+    if highcut is not None and highcut < nyq:
+        if low is not None:
+            return butter(order, [low / nyq, highcut / nyq], analog=False, btype="bandpass", output="sos")
+        return butter(order, highcut / nyq, analog=False, btype="lowpass", output="sos")
+    if low is None:
+        logging.warning("No freq to filter: band [%s, %s] at fs %s", lowcut, highcut, fs)
+        return None
+    logging.warning("Band [%s, %s] reaches Nyquist (%s): high-pass at %s", lowcut, highcut, nyq, lowcut)
+    return butter(order, low / nyq, analog=False, btype="highpass", output="sos")
+
+
+def butter_bandpass_filter(data, lowcut, highcut, fs, order=2):
+    """sosfilt of `data` with butter_bandpass (predict_utils.py:259-262) as
+    float64, from a zero initial state; None when there is no filter."""
+    from scipy.signal import sosfilt
+
+    sos = butter_bandpass(lowcut, highcut, fs, order=order)
+    return None if sos is None else sosfilt(sos, data)
+
+
+def track_sos(t, sr, filter_freqs=False, filter_below=None):
+    """The filter load_samples (:103-113) applies to track t: butter_bandpass of
+    its band when filter_freqs is set, or when filter_below is and the track
+    ends under it; None for a track that stays unfiltered."""
+    if filter_freqs or (filter_below and t.freq_end is not None and t.freq_end < filter_below):
+        return butter_bandpass(t.freq_start, t.freq_end, sr)
+    return None
+
+
 def track_windows(frames, sr, tracks, segment_length=3, stride=1, fmin=100, fmax=11000, pad_short_tracks=False,
-                  rng=None):
+                  rng=None, filter_freqs=False, filter_below=None):
     """The raw 3 s windows predict_utils.load_samples (:59-150) cuts from each
     track (before its normalize / spectrogram, which run on the GPU) ->
     list of [n_i, sr * segment_length] float32 arrays, one per track (empty
-    for tracks wholly outside [fmin, fmax], which are not classified)."""
+    for tracks wholly outside [fmin, fmax], which are not classified).
+    filter_freqs / filter_below (track_sos): the whole clipped slice of the
+    track is filtered before the window loop, from a zero state at its first
+    sample, and cast back to float32, so the state carries across windows."""
+    from scipy.signal import sosfilt
+
     rng = rng if rng is not None else np.random
     sample_size = int(sr * segment_length)
     frames = np.asarray(frames, np.float32)
@@ -122,6 +186,9 @@ def track_windows(frames, sr, tracks, segment_length=3, stride=1, fmin=100, fmax
                     sr_end = end_offset
             track_frames = frames[sr_start:sr_end]
         sr_start, sr_end = 0, min(sr_end, sample_size)
+        sos = track_sos(t, sr, filter_freqs, filter_below)
+        if sos is not None and len(track_frames):
+            track_frames = sosfilt(sos, track_frames).astype(np.float32)
         while True:
             data = track_frames[sr_start:sr_end]
             if len(data) != sample_size:
@@ -140,7 +207,7 @@ def track_windows(frames, sr, tracks, segment_length=3, stride=1, fmin=100, fmax
 
 
 def track_window_plan(n_frames, sr, tracks, segment_length=3, stride=1, fmin=100, fmax=11000, pad_short_tracks=False,
-                      rng=None):
+                      rng=None, segments=False):
     """track_windows as a table instead of copies: the windows it would cut
     from a recording of n_frames samples -> (plan, counts).  plan is int64
     [n_windows, 3] with rows (src, count, pad): window w is
@@ -150,13 +217,17 @@ def track_window_plan(n_frames, sr, tracks, segment_length=3, stride=1, fmin=100
     track_windows' own, its numpy slices clipped as numpy clips them, and
     rng.randint is drawn once per partial window in the same order, so that
     applying the plan reproduces track_windows bit for bit.  An empty window
-    (count 0) has src 0."""
+    (count 0) has src 0.  With segments=True the result is (plan, counts,
+    segs): segs is int64 [n_tracks, 2] with rows (t0, t_len), the samples
+    [t0, t0 + t_len) of the recording that track k's windows are cut from
+    (track_windows' track_frames; (0, 0) for a track without windows)."""
     rng = rng if rng is not None else np.random
     sample_size = int(sr * segment_length)
-    rows, counts = [], []
+    rows, counts, segs = [], [], []
     for t in tracks:
         if t.freq_start is not None and t.freq_end is not None and (t.freq_start > fmax or t.freq_end < fmin):
             counts.append(0)
+            segs.append((0, 0))
             continue
         start, end = 0, segment_length
         sr_end, sr_start = int(t.end * sr), int(sr * t.start)
@@ -179,6 +250,7 @@ def track_window_plan(n_frames, sr, tracks, segment_length=3, stride=1, fmin=100
         # track_frames = frames[sr_start:sr_end]: samples [t0, t0 + t_len) of the recording
         t0, t1, _ = slice(sr_start, sr_end).indices(n_frames)
         t_len = max(0, t1 - t0)
+        segs.append((t0, t_len))
         sr_start, sr_end = 0, min(sr_end, sample_size)
         n_win = 0
         while True:
@@ -194,7 +266,10 @@ def track_window_plan(n_frames, sr, tracks, segment_length=3, stride=1, fmin=100
             if end > t.length:
                 break
         counts.append(n_win)
-    return np.array(rows, np.int64).reshape(-1, 3), counts
+    plan = np.array(rows, np.int64).reshape(-1, 3)
+    if segments:
+        return plan, counts, np.array(segs, np.int64).reshape(-1, 2)
+    return plan, counts
 
 
 def check_window_plan(plan, rec_len, n):
@@ -213,6 +288,76 @@ def check_window_plan(plan, rec_len, n):
         raise ValueError(f"window {w}: (src, count, pad) = {tuple(int(v) for v in plan[w])} does not fit a window "
                          f"of {n} samples in a recording of {rec_len}")
     return plan
+
+
+SOS_IDENTITY = np.array([[1.0, 0, 0, 1, 0, 0]] * 2)
+
+
+def sos_segment_plan(tracks, segs, plan, counts, sr, filter_freqs=False, filter_below=None):
+    """The device form of track_windows' filtering: from the tracks, their
+    segments `segs` and the window table of track_window_plan(segments=True)
+    -> (seg, sos, plan2) for acfe.frontend.sosfilt_segments.
+    seg: int64 [n_seg, 3] rows (src, len, dst), one per track with windows:
+    samples [src, src + len) of the recording are filtered into
+    [dst, dst + len) of one packed buffer, dst rounded up to 4 floats so that
+    every segment starts 16-B aligned (the buffer holds max(dst + len) rounded
+    up likewise).  sos: float64 [n_seg, 2, 6], track_sos of each track with a
+    missing section as the identity (1, 0, 0, 1, 0, 0); an unfiltered track
+    has two and is a copy.  plan2: `plan` with every non-empty window's src
+    rebased into the packed buffer (src - t0 + dst)."""
+    plan2 = np.array(plan, np.int64).reshape(-1, 3)
+    seg, sos = [], []
+    at = dst = 0
+    for t, (t0, t_len), c in zip(tracks, np.asarray(segs, np.int64).reshape(-1, 2).tolist(), counts):
+        if c == 0:
+            continue
+        rows = plan2[at:at + c]
+        rows[rows[:, 1] > 0, 0] += dst - t0
+        at += c
+        f = np.array(SOS_IDENTITY)
+        s = track_sos(t, sr, filter_freqs, filter_below)
+        if s is not None:
+            f[:len(s)] = s
+        seg.append((t0, t_len, dst))
+        sos.append(f)
+        dst = (dst + t_len + 3) & ~3
+    return np.array(seg, np.int64).reshape(-1, 3), np.array(sos, np.float64).reshape(-1, 2, 6), plan2
+
+
+def check_sos_segments(seg, sos, rec_len, out_len):
+    """A segment table and its filters (sos_segment_plan's form) as contiguous
+    int64 / float64, after checking them against a recording of rec_len
+    samples and a packed buffer of out_len: ValueError unless every row has
+    0 <= src, 0 <= len, src + len <= rec_len, 0 <= dst, dst + len <= out_len,
+    the [dst, dst + len) ranges are disjoint, every coefficient is finite and
+    every a0 is 1."""
+    seg = np.ascontiguousarray(seg, np.int64)
+    sos = np.ascontiguousarray(sos, np.float64)
+    if seg.ndim != 2 or seg.shape[1] != 3:
+        raise ValueError(f"segment table must be [n_seg, 3], got {seg.shape}")
+    if sos.shape != (seg.shape[0], 2, 6):
+        raise ValueError(f"sos must be [{seg.shape[0]}, 2, 6], got {sos.shape}")
+    src, ln, dst = seg[:, 0], seg[:, 1], seg[:, 2]
+    # src + len <= rec_len and dst + len <= out_len, written so that no int64 sum can wrap
+    bad = (ln < 0) | (src < 0) | (ln > rec_len) | (src > rec_len - ln) | (dst < 0) | (ln > out_len) | \
+        (dst > out_len - ln)
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"segment {k}: (src, len, dst) = {tuple(int(v) for v in seg[k])} does not fit a recording "
+                         f"of {rec_len} samples and a buffer of {out_len}")
+    order = np.argsort(dst, kind="stable")
+    order = order[ln[order] > 0]
+    # consecutive ranges in dst order: len <= next dst - dst (both in [0, out_len], no wrap)
+    clash = ln[order[:-1]] > dst[order[1:]] - dst[order[:-1]]
+    if clash.any():
+        k = int(order[int(np.flatnonzero(clash)[0])])
+        raise ValueError(f"segment {k}: (src, len, dst) = {tuple(int(v) for v in seg[k])} overlaps the next "
+                         "segment of the buffer")
+    if not np.isfinite(sos).all():
+        raise ValueError("sos holds a non-finite coefficient")
+    if (sos[:, :, 3] != 1.0).any():
+        raise ValueError("sos must be normalised: a0 == 1 in every section")
+    return seg, sos
 
 
 def detect_tracks(frames, sr=SR, detector="host", dev_out=None):
@@ -323,13 +468,19 @@ class Predictor:
             out.append(ops.sigmoid(self.model(self.frontend.features(x, pad_mode="constant"))))
         return torch.cat(out).float().cpu().numpy()
 
-    def predict_tracks(self, frames, threshold=None, batch_size=1024, rng=None, detector="host", windows="host"):
+    def predict_tracks(self, frames, threshold=None, batch_size=1024, rng=None, detector="host", windows="host",
+                       filter_freqs=False, filter_below=None):
         """Tracks of one recording with their ModelResult (predict.py:735-956);
         `detector` as in detect_tracks ("gpu" keeps one SignalDetector per Predictor).
         windows "host" cuts every window with numpy and uploads them; "device"
         computes only the window table on the host and cuts the windows out of
         the device recording (the detector's buffer when detector is "gpu",
-        else one upload) -- the same windows, so the same predictions."""
+        else one upload) -- the same windows, so the same predictions.
+        filter_freqs / filter_below band-pass the tracks first (track_sos):
+        with scipy on the host for windows "host", with
+        frontend.sosfilt_segments into one packed device buffer, which the
+        window kernel then reads by the rebased table, for "device"; when no
+        track is filtered the device path runs as without the options."""
         if windows not in ("host", "device"):
             raise ValueError(f"windows {windows!r}: expected 'host' or 'device'")
         if detector == "gpu":
@@ -342,12 +493,18 @@ class Predictor:
         tracks, frames, end = detect_tracks(np.asarray(frames, np.float32), detector=detector, dev_out=dev)
         thresh = self.meta.get("threshold", 0.7) if threshold is None else threshold
         if windows == "host":
-            wins = track_windows(frames, SR, tracks, rng=rng)
+            wins = track_windows(frames, SR, tracks, rng=rng, filter_freqs=filter_freqs, filter_below=filter_below)
             counts = [len(w) for w in wins]
             probs = self.predict_clips(np.concatenate(wins), batch_size) if sum(counts) else None
         else:
-            plan, counts = track_window_plan(len(frames), SR, tracks, rng=rng)
+            plan, counts, segs = track_window_plan(len(frames), SR, tracks, rng=rng, segments=True)
             rec = dev[0] if dev else torch.from_numpy(np.ascontiguousarray(frames)).to(self.device)
+            if filter_freqs or filter_below:
+                from acfe import frontend as fe
+
+                seg, sos, plan2 = sos_segment_plan(tracks, segs, plan, counts, SR, filter_freqs, filter_below)
+                if (sos != SOS_IDENTITY).any():
+                    rec, plan = fe.sosfilt_segments(rec, seg, sos), plan2
             probs = self.predict_plan(rec, plan, batch_size) if len(plan) else None
         at = 0
         for t, c in zip(tracks, counts):
@@ -390,13 +547,18 @@ def main(argv=None):
     ap.add_argument("--windows", choices=("host", "device"), default="host",
                     help="the 3 s windows of the tracks (--mode tracks): cut with numpy and uploaded, or cut and "
                          "normalised on the GPU from the uploaded recording by the table of window positions")
+    ap.add_argument("--filter-freqs", action="store_true",
+                    help="band-pass every track at its own frequency band before its windows are cut (--mode tracks)")
+    ap.add_argument("--filter-below", type=float, default=None, metavar="HZ",
+                    help="band-pass only the tracks whose band ends below HZ (--mode tracks)")
     a = ap.parse_args(argv)
     p = Predictor(a.model)
     for f in a.file:
         t0 = time.perf_counter()
         if a.mode == "tracks":
             tracks, end = p.predict_tracks(load_recording(f), a.threshold, a.batch_size, detector=a.detector,
-                                           windows=a.windows)
+                                           windows=a.windows, filter_freqs=a.filter_freqs,
+                                           filter_below=a.filter_below)
             r = {"file": str(f), "end": end, "tracks": [t.get_meta() for t in tracks]}
         else:
             r = p.predict_file(f, a.stride, a.batch_size, a.threshold)

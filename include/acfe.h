@@ -36,6 +36,7 @@
  *   acfe_map_runs          identifytracks.py:104     connectedComponentsWithStats (runs; host union)
  *   acfe_chunk_flat        identifytracks.py:41-43   get_end's max == min chunk test
  *   acfe_windows_normalize predict_utils.py:59-160   load_samples' window cut + normalize_data
+ *   acfe_sosfilt_segments  predict_utils.py:103-113, 245-262  load_samples' Butterworth band-pass (sosfilt)
  */
 #ifndef ACFE_H
 #define ACFE_H
@@ -698,6 +699,31 @@ int acfe_chunk_flat(const float* img, int rows, int cols, int chunk, int n_chunk
  * out[b] is written. */
 int acfe_windows_normalize(const float* rec, int64_t rec_len, const int64_t* plan, int batch, int n, float* out,
                            float* stats, void* stream);
+
+/* scipy.signal.sosfilt over segments of a device-resident recording, each
+ * with its own Butterworth filter (predict_utils.py:103-113, 245-262:
+ * load_samples' filter_freqs / filter_below), packed into one float32 buffer
+ * from which acfe_windows_normalize then cuts the windows
+ * (csrc/sosfilt.hip).  seg is a device table [n_seg][3] of int64 {src, len,
+ * dst}, sos a device table [n_seg][2][6] of float64 {b0, b1, b2, a0, a1, a2}
+ * with a0 == 1 (a missing section is the identity 1, 0, 0, 1, 0, 0):
+ *   out[dst + i] = (float)sosfilt(sos_k, (double)rec[src .. src + len))[i],
+ * from a zero state at the segment's first sample, float64 throughout (a
+ * blocked scan of the linear recurrence: before the cast within 1e-9 of
+ * max |y| of the sequential filter for a 100-110 Hz band at 48 kHz, 2e-8 for
+ * 20-24 Hz, i.e. well under a float32 ulp).  A segment whose two sections are both
+ * the identity is copied bit for bit.  ws: acfe_sosfilt_workspace(out_len,
+ * n_seg) bytes, about out_len + 10 KiB per segment; ACFE_E_INVAL from both
+ * calls for a negative size.  A valid table has 0 <= src, 0 <= len, src + len
+ * <= rec_len and disjoint [dst, dst + len) inside out[0, out_len) (16-B
+ * aligned dst keeps every store 16 B wide); whatever the table holds, nothing
+ * outside rec[0, rec_len) is read (such a sample counts as zero) and nothing
+ * outside out[0, out_len) is written: len is clamped to [0, out_len - dst],
+ * and a row whose dst lies outside [0, out_len] writes nothing.  out elements
+ * no segment covers are left alone. */
+int64_t acfe_sosfilt_workspace(int64_t total_len, int n_seg);
+int acfe_sosfilt_segments(const float* rec, int64_t rec_len, const int64_t* seg, const double* sos, int n_seg,
+                          float* out, int64_t out_len, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

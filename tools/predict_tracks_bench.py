@@ -18,7 +18,24 @@ length; one JSON line per length.
             device alternating: every time is listed, the ratio is of the minima.
   The whole call likewise: WHOLE_REPS timed calls per setting, alternating.
 
-  python tools/predict_tracks_bench.py [--seconds 60 600] [--batch-size 1024]
+--filter-freqs measures the Butterworth band-pass of the tracks
+(predict_tracks(filter_freqs=True)) instead, one JSON line per length:
+
+  whole_s          the whole call with the option on, windows "host" (scipy
+                   sosfilt inside track_windows) against "device"
+                   (sosfilt_segments + the window kernel), alternating
+  host_filter_s    wall clock of the host filter stage alone: sosfilt + the
+                   float32 cast of every track segment (FILTER_REPS runs after
+                   one untimed)
+  device_filter_ms HIP events around frontend.sosfilt_segments on the
+                   detector's buffer (table upload, workspace, four kernels);
+                   device_filter_wall_s the same call by wall clock with a
+                   device synchronise at both ends
+  filter_err       max |device - float32(host)| / max |host| over the segments,
+                   in units of 2^-22 (the test bound)
+  prob_diff        max |p_device - p_host| over all windows and classes
+
+  python tools/predict_tracks_bench.py [--seconds 60 600] [--batch-size 1024] [--filter-freqs]
 """
 from __future__ import annotations
 
@@ -40,6 +57,7 @@ SR = 48000
 N = 3 * SR
 STAGE_REPS = 3
 WHOLE_REPS = 2
+FILTER_REPS = 5
 
 
 def make_checkpoint(d, device):
@@ -79,10 +97,69 @@ def timed(fn):
     return round(time.perf_counter() - t0, 5)
 
 
+def filter_report(p, predict, fe, it, x, seconds, batch_size):
+    from scipy.signal import sosfilt
+
+    r = {"seconds": seconds, "gpu": torch.cuda.get_device_name(0), "batch_size": batch_size, "filter_freqs": True}
+    whole = {"host": [], "device": []}
+    boxes = {}
+    for _ in range(WHOLE_REPS):
+        for windows in ("host", "device"):
+            it.Signal._next_id = 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            tracks, end = p.predict_tracks(x, rng=np.random.RandomState(0), detector="gpu", windows=windows,
+                                           batch_size=batch_size, filter_freqs=True)
+            torch.cuda.synchronize()
+            whole[windows].append(round(time.perf_counter() - t0, 4))
+            boxes[windows] = [(t.start, t.end, t.freq_start, t.freq_end, len(t.predictions)) for t in tracks]
+    r["host_whole_s"], r["device_whole_s"] = whole["host"], whole["device"]
+    r["tracks"], r["same_tracks"] = len(boxes["host"]), boxes["host"] == boxes["device"]
+    dev = []
+    tracks, frames, end = predict.detect_tracks(x, detector=p._detector, dev_out=dev)
+    plan, counts, segs = predict.track_window_plan(len(frames), SR, tracks, rng=np.random.RandomState(0),
+                                                   segments=True)
+    seg, sos, plan2 = predict.sos_segment_plan(tracks, segs, plan, counts, SR, filter_freqs=True)
+    r["windows"], r["segments"], r["filtered_samples"] = len(plan), len(seg), int(seg[:, 1].sum())
+    r["recording_samples"] = len(frames)
+
+    def host_filter():
+        return [sosfilt(f, frames[a:a + n]).astype(np.float32) for (a, n, _), f in zip(seg.tolist(), sos)]
+
+    for k in range(FILTER_REPS + 1):
+        t0 = time.perf_counter()
+        ref = host_filter()
+        dt = round(time.perf_counter() - t0, 5)
+        wall = timed(lambda: fe.sosfilt_segments(dev[0], seg, sos))
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        filtered = fe.sosfilt_segments(dev[0], seg, sos)
+        e1.record()
+        torch.cuda.synchronize()
+        if k:  # the first run of each is not counted
+            r.setdefault("host_filter_s", []).append(dt)
+            r.setdefault("device_filter_wall_s", []).append(wall)
+            r.setdefault("device_filter_ms", []).append(round(e0.elapsed_time(e1), 4))
+    buf = filtered.cpu().numpy()
+    err = 0.0
+    for (a, n, d), f, h in zip(seg.tolist(), sos, ref):
+        m = np.abs(sosfilt(f, frames[a:a + n])).max()
+        err = max(err, float(np.abs(buf[d:d + n].astype(np.float64) - h).max() / m) * 2.0 ** 22)
+    r["filter_err"] = round(err, 4)
+    wins = np.concatenate(predict.track_windows(frames, SR, tracks, rng=np.random.RandomState(0), filter_freqs=True))
+    probs = p.predict_plan(filtered, plan2, batch_size), p.predict_clips(wins, batch_size)
+    r["prob_diff"] = float(np.abs(probs[0] - probs[1]).max())
+    r["filter_speedup_events"] = round(min(r["host_filter_s"]) * 1e3 / min(r["device_filter_ms"]), 1)
+    r["filter_speedup_wall"] = round(min(r["host_filter_s"]) / min(r["device_filter_wall_s"]), 1)
+    r["whole_speedup"] = round(min(r["host_whole_s"]) / min(r["device_whole_s"]), 2)
+    print(json.dumps(r), flush=True)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--seconds", type=int, nargs="+", default=[60, 600])
     ap.add_argument("--batch-size", type=int, default=1024)
+    ap.add_argument("--filter-freqs", action="store_true", help="measure the band-pass of the tracks instead")
     a = ap.parse_args(argv)
     import identifytracks as it
     import predict
@@ -95,9 +172,12 @@ def main(argv=None):
         p = predict.Predictor(tmp, device=device)
     for windows in ("host", "device"):  # warm-up: kernels loaded, plans made, allocator filled
         p.predict_tracks(synthetic(10), rng=np.random.RandomState(0), detector="gpu", windows=windows,
-                         batch_size=a.batch_size)
+                         batch_size=a.batch_size, filter_freqs=a.filter_freqs)
     for seconds in a.seconds:
         x = synthetic(seconds)
+        if a.filter_freqs:
+            filter_report(p, predict, fe, it, x, seconds, a.batch_size)
+            continue
         r = {"seconds": seconds, "gpu": torch.cuda.get_device_name(0), "batch_size": a.batch_size}
         metas = {}
         whole = {"host": [], "device": []}
