@@ -25,4 +25,17 @@ Parity pinning:
     librosa, keras -- unpinned in requirements.txt:1-13) that are absent from
     this image; they are restated from their published definitions and are
     "parity unpinned" beyond the golden mel filterbank.
+  * `torch_ref.pcen_torch` follows TF at the clamp edges: MinimumGrad /
+    MaximumGrad give the whole gradient to gain / root at exactly 1.0 (and
+    none beyond), clip_by_value passes it on [0, 1]; amax / amin share it
+    among tied extrema (tests/test_frontend_cases.py).
+  * `frontend_cases` is the table of front-end edge cases (PCEN shapes around
+    the 64-row workgroup and the 32-step chunk, ten parameter sets, per-probe
+    gradients; mel plans with odd / single / long / empty / DC / Nyquist
+    bands; n_fft 2048 / 512 / 256).  Its conditions hold on the reference
+    alone (measured: gap under the maximum >= 2.2e-4 of the range, weakest
+    probe 1.25e-3 of the strongest, float32 noise of the reference
+    <= 6.1e-4 * s); the kernels measure <= 1.9e-6 (PCEN output),
+    <= 6.5e-4 * s (gradients, bound 2e-3 * s) and <= 8.4e-7 (mel, bound
+    2e-5) against it (tests/test_frontend_edges_gpu.py).
 """

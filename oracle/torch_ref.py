@@ -5,15 +5,23 @@ from __future__ import annotations
 import torch
 
 
-def pcen_torch(mel_btm: torch.Tensor, params: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
+def pcen_torch(mel_btm: torch.Tensor, params: torch.Tensor, eps: float = 1e-6, scope_minmax=None) -> torch.Tensor:
     """tfpcen.py:33-39 (EMA via sequential scan), :89-95 (PCEN.call),
     :105-110 (normalize_minmax).  mel [B,T,M] -> [B,M,T] (transposed to the
     model layout).  Differentiable w.r.t. params = {gain, bias, root, smooth};
     torch.amax/amin share the gradient equally among ties, like TF's
-    reduce_max/reduce_min gradients."""
-    gain = torch.minimum(params[0], torch.ones((), dtype=params.dtype))
+    reduce_max/reduce_min gradients.  tf.minimum(gain, 1) / tf.maximum(root, 1)
+    give the WHOLE gradient to the variable at a tie (MinimumGrad: x <= y,
+    MaximumGrad: x >= y) and none beyond; torch.minimum / torch.maximum halve
+    it at the tie, so the choice is made with torch.where on the parameter.
+    torch.clamp passes the gradient on the closed interval, as
+    tf.clip_by_value does.  scope_minmax = (mn, mx) replaces the batch
+    extrema with constants (the acfe_pcen_normalize scope: no gradient through
+    them)."""
+    one = torch.ones((), dtype=params.dtype)
+    gain = torch.where(params[0] <= 1.0, params[0], one)
     bias = params[1]
-    root = torch.maximum(params[2], torch.ones((), dtype=params.dtype))
+    root = torch.where(params[2] >= 1.0, params[2], one)
     w = torch.clamp(params[3], 0.0, 1.0)
     x = mel_btm.to(params.dtype)
     a = x[:, 0]
@@ -24,7 +32,10 @@ def pcen_torch(mel_btm: torch.Tensor, params: torch.Tensor, eps: float = 1e-6) -
     ema = torch.stack(outs, dim=1)
     inv_r = 1.0 / root
     y = (x / (eps + ema) ** gain + bias) ** inv_r - bias ** inv_r
-    mx, mn = torch.amax(y), torch.amin(y)
+    if scope_minmax is None:
+        mx, mn = torch.amax(y), torch.amin(y)
+    else:
+        mn, mx = (torch.as_tensor(v, dtype=params.dtype) for v in scope_minmax)
     out = 2 * ((y - mn) / (mx - mn)) - 1
     return out.transpose(1, 2)
 

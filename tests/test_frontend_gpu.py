@@ -3,7 +3,9 @@
 Tolerances (fp32 kernels vs float64 oracle):
   mel:   |gpu - ref| <= 2e-5 * max(ref) per clip  (fp32 FFT, 11 passes)
   PCEN:  |gpu - ref| <= 5e-5 on the [-1, 1] output
-  dPCEN: relative 2e-3 on parameter gradients (fp32 accumulation over B*M*T)
+  dPCEN: relative 2e-3 on parameter gradients (fp32 accumulation over B*M*T);
+         per probe (one column, one row, one element of dout) instead of per
+         sum, at row / chunk / clamp edges: tests/test_frontend_edges_gpu.py
 """
 import numpy as np
 import pytest
