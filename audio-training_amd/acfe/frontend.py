@@ -222,6 +222,46 @@ def sosfilt_segments(rec: torch.Tensor, seg, sos, out: torch.Tensor | None = Non
     return out
 
 
+_RESAMPLE_TAPS: dict = {}  # (rate, sr, device) -> (ResamplePlan, its taps on the device)
+
+
+def resample_poly(x: torch.Tensor, rate: int, sr: int = 48000, out: torch.Tensor | None = None) -> torch.Tensor:
+    """scipy.signal.resample_poly(x, sr // g, rate // g), g = gcd(rate, sr), of
+    the 1-D device recording `x` sampled at `rate` -> float32 [n_out] at `sr`
+    (the resampling of predict.load_recording, on the device).  x is float32,
+    or int16 PCM, which enters as float32(v) / 32767 -- bit-identical to
+    converting on the host first.  The taps and the index arithmetic are
+    scipy's (predict.resample_plan; the taps are uploaded once per (rate, sr,
+    device)); every output is summed in float64 and rounded to float32 once
+    (csrc/resample.hip).  rate == sr returns a float32 x itself and converts
+    an int16 x with the same kernel.  ValueError for a rate whose filter has
+    more taps than the kernel stages (plan.device is False)."""
+    from predict import resample_plan  # host-only filter design and index arithmetic
+
+    require_cuda(x, out)
+    if x.dim() != 1 or x.dtype not in (torch.float32, torch.int16):
+        raise TypeError("the recording must be a contiguous 1-D float32 or int16 tensor")
+    key = (int(rate), int(sr), x.device)
+    if key not in _RESAMPLE_TAPS:
+        plan = resample_plan(rate, sr)
+        _RESAMPLE_TAPS[key] = (plan, torch.from_numpy(plan.h).to(x.device) if plan.device else None)
+    plan, taps = _RESAMPLE_TAPS[key]
+    if not plan.device:
+        raise ValueError(f"{rate} -> {sr} Hz needs {len(plan.h)} filter taps, more than the device resampler's "
+                         "16384: resample on the host")
+    n_out = plan.n_out(x.numel())
+    if out is not None and (tuple(out.shape) != (n_out,) or out.dtype != torch.float32):
+        raise ValueError("bad out tensor")
+    if plan.up == plan.down and x.dtype == torch.float32 and out is None:
+        return x
+    if out is None:
+        out = torch.empty(n_out, dtype=torch.float32, device=x.device)
+    code = _lib.DTYPE_F32 if x.dtype == torch.float32 else _lib.DTYPE_I16
+    call("acfe_resample_poly", ptr(x), code, x.numel(), ptr(taps), len(plan.h), plan.up, plan.down, plan.t0,
+         ptr(out), n_out, stream())
+    return out
+
+
 def mix_up(x1, x2, lam, stats1=None, stats2=None) -> torch.Tensor:
     """tfdataset.mix_up image blend (tfdataset.py:950); lam [B] fp32 on device."""
     require_cuda(x1, x2, lam, stats1, stats2)

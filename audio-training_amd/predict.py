@@ -3,10 +3,18 @@
 predict_utils.py:9-239).
 
   python predict.py --file REC.wav CHECKPOINT_DIR [--stride 1] [--batch-size 1024] [--detector gpu]
-                    [--windows device] [--filter-freqs | --filter-below HZ]
+                    [--windows device] [--filter-freqs | --filter-below HZ] [--resample device]
 
 The recording is decoded on the host (WAV via scipy; the reference's ffmpeg /
-librosa loader is out of scope) and resampled to 48 kHz.
+librosa loader is out of scope) and resampled to 48 kHz: with scipy's
+resample_poly on the host (--resample host, the default), or with --resample
+device by the HIP kernel of acfe_resample_poly, which applies the same taps at
+the same indices to the uploaded samples (an int16 mono file is uploaded as
+int16, half the bytes) and sums every output in float64.  The 48 kHz
+recording is then a device tensor: with --detector gpu and --windows device
+it never passes through host memory, otherwise it is downloaded once.  A rate
+whose filter is longer than 16384 taps (44 101 Hz, say) is resampled on the
+host with a warning.
 
 --mode tracks (default, the reference's predict.py:735-956): the digitally
 silent tail is cut (get_end) and signals are detected -- on the host with
@@ -63,17 +71,88 @@ import torch  # noqa: E402
 SR = 48000
 
 
-def load_recording(path, sr=SR):
-    """predict.load_recording (predict.py:59-66) for WAV input."""
-    from scipy.io import wavfile
-    from scipy.signal import resample_poly
+RESAMPLE_MAX_TAPS = 16384  # what acfe_resample_poly stages in LDS (64 KiB of float32 taps)
 
-    rate, data = wavfile.read(path)
+
+class ResamplePlan:
+    """The FIR taps and index arithmetic of scipy.signal.resample_poly(x, up,
+    down) for a float32 x and its default window and padding (resample_plan).
+    With x[j] = 0 outside [0, n_in):
+      t = n * down + t0;  p = t % up;  j0 = t // up
+      out[n] = sum over k >= 0 with p + k * up < len(h) of h[p + k * up] * x[j0 - k]
+    for n < n_out(n_in).  device: whether acfe.frontend.resample_poly takes
+    the plan (len(h) <= RESAMPLE_MAX_TAPS)."""
+
+    def __init__(self, rate, sr, up, down, h, t0):
+        self.rate, self.sr, self.up, self.down, self.h, self.t0 = rate, sr, up, down, h, t0
+        self.terms = -(-len(h) // up)  # the most taps that meet one output (K)
+        self.device = len(h) <= RESAMPLE_MAX_TAPS
+
+    def n_out(self, n_in):
+        return -(-int(n_in) * self.up // self.down)
+
+
+def resample_plan(rate, sr=SR):
+    """What resample_poly(x, sr // g, rate // g), g = gcd(rate, sr), computes
+    with, as a ResamplePlan: scipy's own float32 taps (firwin over
+    2 * half_len + 1 points with a Kaiser(5.0) window, times up) bit for bit,
+    and the offset t0 that its zero pre-padding of h and the outputs it then
+    drops amount to.  rate == sr is the identity: the one tap 1.0, t0 = 0."""
+    from scipy.signal import firwin
+
+    rate, sr = int(rate), int(sr)
+    if rate < 1 or sr < 1:
+        raise ValueError(f"sample rates must be positive, got {rate} -> {sr}")
+    g = math.gcd(rate, sr)
+    up, down = sr // g, rate // g
+    if up == down:
+        return ResamplePlan(rate, sr, 1, 1, np.ones(1, np.float32), 0)
+    half_len = 10 * max(up, down)
+    h = firwin(2 * half_len + 1, 1.0 / max(up, down), window=("kaiser", 5.0)).astype(np.float32)
+    h *= up
+    n_pre_pad = down - half_len % down
+    n_pre_remove = (half_len + n_pre_pad) // down
+    return ResamplePlan(rate, sr, up, down, h, n_pre_remove * down - n_pre_pad)
+
+
+def _float_mono(data):
+    """Decoded WAV samples as float32 mono: integer PCM over its positive
+    full scale, channels averaged."""
     if np.issubdtype(data.dtype, np.integer):
         data = data.astype(np.float32) / float(np.iinfo(data.dtype).max)
     data = data.astype(np.float32)
     if data.ndim > 1:
         data = data.mean(1)
+    return data
+
+
+def load_recording(path, sr=SR, resample="host", device=None):
+    """predict.load_recording (predict.py:59-66) for WAV input -> float32
+    samples at `sr`.  resample "host": scipy's resample_poly, a numpy array.
+    "device": the decoded samples are uploaded to `device` (default: the
+    current one) -- an int16 mono file as int16, anything else as float32
+    after the host conversion and channel mean -- and resampled there by
+    acfe.frontend.resample_poly; the result is a 1-D float32 device tensor
+    (also for a file already at `sr`, which is only uploaded).  A rate whose
+    filter the kernel does not take (resample_plan(rate, sr).device is False)
+    logs one warning and gives the host result."""
+    from scipy.io import wavfile
+    from scipy.signal import resample_poly
+
+    if resample not in ("host", "device"):
+        raise ValueError(f"resample {resample!r}: expected 'host' or 'device'")
+    rate, data = wavfile.read(path)
+    if resample == "device":
+        if resample_plan(rate, sr).device:
+            from acfe import frontend as fe
+
+            device = device or torch.device("cuda", torch.cuda.current_device())
+            if data.dtype != np.int16 or data.ndim != 1:
+                data = _float_mono(data)
+            return fe.resample_poly(torch.from_numpy(np.ascontiguousarray(data)).to(device), rate, sr)
+        logging.warning("%s: %d -> %d Hz needs more than %d filter taps, resampling on the host", path, rate, sr,
+                        RESAMPLE_MAX_TAPS)
+    data = _float_mono(data)
     if rate != sr:
         g = math.gcd(rate, sr)
         data = resample_poly(data, sr // g, rate // g).astype(np.float32)
@@ -360,6 +439,16 @@ def check_sos_segments(seg, sos, rec_len, out_len):
     return seg, sos
 
 
+def host_frames(frames):
+    """A recording as numpy: a 1-D float32 device tensor is downloaded, numpy
+    input passes through."""
+    if isinstance(frames, torch.Tensor):
+        if frames.dim() != 1 or frames.dtype != torch.float32:
+            raise TypeError("a recording tensor must be 1-D float32")
+        return frames.detach().cpu().numpy()
+    return frames
+
+
 def detect_tracks(frames, sr=SR, detector="host", dev_out=None):
     """predict.main (:735-740): cut the silent tail, detect signals, merge
     them into tracks -> (tracks, frames[:end], end seconds).  detector "host"
@@ -368,10 +457,14 @@ def detect_tracks(frames, sr=SR, detector="host", dev_out=None):
     the device, the cut recording being a slice of that one buffer.  The
     merging into tracks is host work on a few hundred boxes either way.
     A device detector appends that slice, the cut recording on the device,
-    to the list `dev_out` when one is given."""
+    to the list `dev_out` when one is given.  `frames` may be a 1-D float32
+    device tensor (load_recording(resample="device")): a device detector uses
+    it where it lies and the returned frames are a slice of it; the host
+    detector downloads it first."""
     from identifytracks import get_end, get_tracks_from_signals, signal_noise
 
     if detector == "host":
+        frames = host_frames(frames)
         end = get_end(frames, sr)
         frames = frames[: int(sr * end)]
         signals, _ = signal_noise(frames, sr)
@@ -422,17 +515,26 @@ class Predictor:
         self._detector = None  # acfe.tracks.SignalDetector of predict_tracks(detector="gpu")
 
     @torch.no_grad()
-    def predict_windows(self, recording: np.ndarray, stride=1.0, batch_size=1024, pad_mode="constant"):
-        """Sigmoid outputs [n_windows, classes] for 3 s windows every `stride` s."""
+    def predict_windows(self, recording, stride=1.0, batch_size=1024, pad_mode="constant"):
+        """Sigmoid outputs [n_windows, classes] for 3 s windows every `stride` s
+        of a numpy recording, or of a 1-D float32 device tensor, which is read
+        where it lies."""
         from acfe import ops
 
         n = SR * 3
-        rec = np.asarray(recording, np.float32)
-        if len(rec) < n:  # short recordings are zero padded to one window
-            rec = np.pad(rec, (0, n - len(rec)))
+        if isinstance(recording, torch.Tensor):
+            if recording.dim() != 1 or recording.dtype != torch.float32:
+                raise TypeError("a recording tensor must be 1-D float32")
+            dev_rec = recording.to(self.device).contiguous()
+            if dev_rec.numel() < n:  # short recordings are zero padded to one window
+                dev_rec = torch.nn.functional.pad(dev_rec, (0, n - dev_rec.numel()))
+        else:
+            rec = np.asarray(recording, np.float32)
+            if len(rec) < n:
+                rec = np.pad(rec, (0, n - len(rec)))
+            dev_rec = torch.from_numpy(rec).to(self.device)
         hop = int(round(stride * SR))
-        n_win = 1 + (len(rec) - n) // hop
-        dev_rec = torch.from_numpy(rec).to(self.device)
+        n_win = 1 + (dev_rec.numel() - n) // hop
         out = []
         for first in range(0, n_win, batch_size):
             cnt = min(batch_size, n_win - first)
@@ -480,9 +582,15 @@ class Predictor:
         with scipy on the host for windows "host", with
         frontend.sosfilt_segments into one packed device buffer, which the
         window kernel then reads by the rebased table, for "device"; when no
-        track is filtered the device path runs as without the options."""
+        track is filtered the device path runs as without the options.
+        `frames` may be a 1-D float32 device tensor
+        (load_recording(resample="device")): with detector "gpu" and windows
+        "device" its samples never visit the host; with a host detector or
+        host windows it is downloaded once and the call goes on as for numpy."""
         if windows not in ("host", "device"):
             raise ValueError(f"windows {windows!r}: expected 'host' or 'device'")
+        if isinstance(frames, torch.Tensor) and (detector == "host" or windows == "host"):
+            frames = host_frames(frames)
         if detector == "gpu":
             if self._detector is None:
                 from acfe.tracks import SignalDetector
@@ -490,7 +598,9 @@ class Predictor:
                 self._detector = SignalDetector(device=self.device, sr=SR)
             detector = self._detector
         dev = []
-        tracks, frames, end = detect_tracks(np.asarray(frames, np.float32), detector=detector, dev_out=dev)
+        if not isinstance(frames, torch.Tensor):
+            frames = np.asarray(frames, np.float32)
+        tracks, frames, end = detect_tracks(frames, detector=detector, dev_out=dev)
         thresh = self.meta.get("threshold", 0.7) if threshold is None else threshold
         if windows == "host":
             wins = track_windows(frames, SR, tracks, rng=rng, filter_freqs=filter_freqs, filter_below=filter_below)
@@ -526,8 +636,8 @@ class Predictor:
                 r.raw_confidence = round(float(max_p[1]) * 100)
         return tracks, end
 
-    def predict_file(self, path, stride=1.0, batch_size=1024, threshold=0.7):
-        probs = self.predict_windows(load_recording(path), stride, batch_size)
+    def predict_file(self, path, stride=1.0, batch_size=1024, threshold=0.7, resample="host"):
+        probs = self.predict_windows(load_recording(path, resample=resample, device=self.device), stride, batch_size)
         mean = probs.mean(0)
         labels = [(self.labels[i], float(mean[i])) for i in np.argsort(-mean) if mean[i] >= threshold]
         return {"file": str(path), "windows": int(probs.shape[0]), "labels": labels,
@@ -551,17 +661,20 @@ def main(argv=None):
                     help="band-pass every track at its own frequency band before its windows are cut (--mode tracks)")
     ap.add_argument("--filter-below", type=float, default=None, metavar="HZ",
                     help="band-pass only the tracks whose band ends below HZ (--mode tracks)")
+    ap.add_argument("--resample", choices=("host", "device"), default="host",
+                    help="resampling of a recording that is not at 48 kHz: scipy's resample_poly on the host, or the "
+                         "same filter as a HIP kernel on the uploaded samples (the recording then stays on the GPU)")
     a = ap.parse_args(argv)
     p = Predictor(a.model)
     for f in a.file:
         t0 = time.perf_counter()
         if a.mode == "tracks":
-            tracks, end = p.predict_tracks(load_recording(f), a.threshold, a.batch_size, detector=a.detector,
-                                           windows=a.windows, filter_freqs=a.filter_freqs,
-                                           filter_below=a.filter_below)
+            rec = load_recording(f, resample=a.resample, device=p.device)
+            tracks, end = p.predict_tracks(rec, a.threshold, a.batch_size, detector=a.detector, windows=a.windows,
+                                           filter_freqs=a.filter_freqs, filter_below=a.filter_below)
             r = {"file": str(f), "end": end, "tracks": [t.get_meta() for t in tracks]}
         else:
-            r = p.predict_file(f, a.stride, a.batch_size, a.threshold)
+            r = p.predict_file(f, a.stride, a.batch_size, a.threshold, resample=a.resample)
         r["seconds"] = round(time.perf_counter() - t0, 3)
         print(json.dumps(r, default=float))
 

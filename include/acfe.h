@@ -37,6 +37,7 @@
  *   acfe_chunk_flat        identifytracks.py:41-43   get_end's max == min chunk test
  *   acfe_windows_normalize predict_utils.py:59-160   load_samples' window cut + normalize_data
  *   acfe_sosfilt_segments  predict_utils.py:103-113, 245-262  load_samples' Butterworth band-pass (sosfilt)
+ *   acfe_resample_poly     predict.py:59-66          load_recording's resampling to 48 kHz (as resample_poly)
  */
 #ifndef ACFE_H
 #define ACFE_H
@@ -62,6 +63,7 @@ extern "C" {
 
 #define ACFE_DTYPE_F32 0
 #define ACFE_DTYPE_BF16 1
+#define ACFE_DTYPE_I16 2 /* PCM samples, acfe_resample_poly's input only */
 
 typedef struct acfe_plan_s* acfe_plan_t;
 
@@ -724,6 +726,29 @@ int acfe_windows_normalize(const float* rec, int64_t rec_len, const int64_t* pla
 int64_t acfe_sosfilt_workspace(int64_t total_len, int n_seg);
 int acfe_sosfilt_segments(const float* rec, int64_t rec_len, const int64_t* seg, const double* sos, int n_seg,
                           float* out, int64_t out_len, void* ws, void* stream);
+
+/* scipy.signal.resample_poly(x, up, down) of a device-resident recording
+ * (predict.py:59-66: load_recording's resampling to the model's rate, for
+ * which this project uses resample_poly on the host; csrc/resample.hip).
+ * h[n_taps] are the float32 FIR taps already scaled by up, t0 the offset of
+ * output 0 on the up-sampled time axis (predict.resample_plan computes both
+ * as scipy does), and with x[j] = 0 outside [0, n_in)
+ *   t = n * down + t0,  p = t % up,  j0 = t / up,
+ *   out[n] = (float)(sum over k >= 0 with p + k * up < n_taps of
+ *                    (double)h[p + k * up] * (double)x[j0 - k])
+ * for n < n_out: every product is exact in float64, the sum is taken in
+ * float64 and rounded to float32 once, so the result is within one rounding
+ * of the exact sum whatever the order of the terms.  x_dtype is
+ * ACFE_DTYPE_F32, or ACFE_DTYPE_I16 for PCM samples v that enter as
+ * (float)v / 32767.0f (IEEE division: bit-identical to converting first).
+ * All sample indices are 64-bit.  n_out == 0 is a no-op; n_in == 0 writes
+ * n_out zeros.  ACFE_E_INVAL, before any launch, for up < 1, down < 1,
+ * n_taps < 1, n_taps > 16384 (the taps are staged in 64 KiB of LDS), t0 < 0,
+ * a negative length, an n_out whose t would pass 2^63, or another dtype.
+ * Whatever the arguments, nothing outside x[0, n_in) and h[0, n_taps) is read
+ * and nothing outside out[0, n_out) is written. */
+int acfe_resample_poly(const void* x, int x_dtype, int64_t n_in, const float* h, int n_taps, int up, int down,
+                       int64_t t0, float* out, int64_t n_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -35,7 +35,28 @@ length; one JSON line per length.
                    in units of 2^-22 (the test bound)
   prob_diff        max |p_device - p_host| over all windows and classes
 
-  python tools/predict_tracks_bench.py [--seconds 60 600] [--batch-size 1024] [--filter-freqs]
+--rate HZ (other than 48000) measures the resampling to 48 kHz instead
+(load_recording(resample="host" | "device")), on the same synthetic recording
+generated at HZ and written as an int16 mono WAV; one JSON line per length:
+
+  host_resample_s    wall clock of scipy.signal.resample_poly on the float32
+                     samples (RESAMPLE_REPS runs after one untimed)
+  upload_s           wall clock of the upload of the decoded samples, int16 (what
+                     the device path uploads) and float32 at 48 kHz (what the
+                     host path uploads afterwards), a device synchronise at
+                     both ends
+  device_resample_ms HIP events around frontend.resample_poly on the uploaded
+                     int16 samples; device_resample_wall_s the same call by wall
+                     clock with a device synchronise at both ends
+  whole_s            load_recording + predict_tracks(detector="gpu",
+                     windows="device") by wall clock, resample "host" against
+                     "device", alternating
+  resample_diff      max |device - host| over the 48 kHz samples, and the same
+                     as a fraction of the test bound of that sample
+                     ((K + 3) 2^-24 sum |h x| + ...), from the first 2^20 outputs
+  tracks, same_tracks, prob_diff   of the two whole calls
+
+  python tools/predict_tracks_bench.py [--seconds 60 600] [--batch-size 1024] [--filter-freqs] [--rate HZ]
 """
 from __future__ import annotations
 
@@ -58,6 +79,7 @@ N = 3 * SR
 STAGE_REPS = 3
 WHOLE_REPS = 2
 FILTER_REPS = 5
+RESAMPLE_REPS = 5
 
 
 def make_checkpoint(d, device):
@@ -155,11 +177,100 @@ def filter_report(p, predict, fe, it, x, seconds, batch_size):
     print(json.dumps(r), flush=True)
 
 
+def resample_report(p, predict, fe, it, seconds, rate, batch_size, tmp):
+    from scipy.io import wavfile
+    from scipy.signal import resample_poly
+    from tracks_bench import synthetic
+
+    device = p.device
+    plan = predict.resample_plan(rate)
+    pcm = (synthetic(seconds, sr=rate) * 32767).astype(np.int16)
+    path = Path(tmp) / f"rec_{rate}_{seconds}.wav"
+    wavfile.write(path, rate, pcm)
+    xf = pcm.astype(np.float32) / 32767.0
+    r = {"seconds": seconds, "rate": rate, "up": plan.up, "down": plan.down, "taps": len(plan.h),
+         "gpu": torch.cuda.get_device_name(0), "batch_size": batch_size, "samples_in": len(pcm),
+         "samples_out": plan.n_out(len(pcm))}
+    dev16 = torch.from_numpy(pcm).to(device)
+    for k in range(RESAMPLE_REPS + 1):
+        t0 = time.perf_counter()
+        host = resample_poly(xf, plan.up, plan.down).astype(np.float32)
+        dt = round(time.perf_counter() - t0, 5)
+        up16 = timed(lambda: torch.from_numpy(pcm).to(device))
+        up32 = timed(lambda: torch.from_numpy(host).to(device))
+        wall = timed(lambda: fe.resample_poly(dev16, rate))
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        got = fe.resample_poly(dev16, rate)
+        e1.record()
+        torch.cuda.synchronize()
+        if k:  # the first run of each is not counted
+            r.setdefault("host_resample_s", []).append(dt)
+            r.setdefault("upload_int16_s", []).append(up16)
+            r.setdefault("upload_float32_48k_s", []).append(up32)
+            r.setdefault("device_resample_wall_s", []).append(wall)
+            r.setdefault("device_resample_ms", []).append(round(e0.elapsed_time(e1), 4))
+    g = got.cpu().numpy()
+    diff = np.abs(g.astype(np.float64) - host.astype(np.float64))
+    n = np.arange(min(len(g), 1 << 20), dtype=np.int64)
+    t = n * plan.down + plan.t0
+    q, j0 = t % plan.up, t // plan.up
+    amp, ref = np.zeros(len(n)), np.zeros(len(n))
+    for k in range(plan.terms):
+        ih, jx = q + k * plan.up, j0 - k
+        ok = (ih < len(plan.h)) & (jx >= 0) & (jx < len(xf))
+        term = plan.h[ih[ok]].astype(np.float64) * xf[jx[ok]].astype(np.float64)
+        ref[ok] += term
+        amp[ok] += np.abs(term)
+    bound = 2.0 ** -24 * np.abs(ref) + 2.0 ** -45 * amp + 2.0 ** -149 + (plan.terms + 2) * 2.0 ** -24 * amp
+    r["resample_diff"] = float(diff.max())
+    r["resample_diff_of_bound"] = round(float((diff[:len(n)] / bound).max()), 4)
+    r["device_of_formula_bound"] = round(float((np.abs(g[:len(n)] - ref) / (bound - (plan.terms + 2) * 2.0 ** -24 * amp)
+                                                ).max()), 4)
+
+    probs = {}
+    orig = p.predict_plan
+
+    def spy(*a, **k):
+        probs[mode] = orig(*a, **k)
+        return probs[mode]
+
+    p.predict_plan = spy
+    whole = {"host": [], "device": []}
+    boxes = {}
+    for _ in range(WHOLE_REPS + 1):
+        for mode in ("host", "device"):
+            it.Signal._next_id = 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rec = predict.load_recording(path, resample=mode, device=device)
+            t1 = time.perf_counter()
+            tracks, end = p.predict_tracks(rec, rng=np.random.RandomState(0), detector="gpu", windows="device",
+                                           batch_size=batch_size)
+            torch.cuda.synchronize()
+            whole[mode].append((round(time.perf_counter() - t0, 4), round(t1 - t0, 4)))
+            boxes[mode] = [(t.start, t.end, t.freq_start, t.freq_end, len(t.predictions)) for t in tracks]
+    p.predict_plan = orig
+    for mode in whole:  # the first pair is the warm-up of this length
+        r[f"{mode}_whole_s"] = [w for w, _ in whole[mode][1:]]
+        r[f"{mode}_load_s"] = [l for _, l in whole[mode][1:]]
+    r["tracks"] = [len(boxes["host"]), len(boxes["device"])]
+    r["same_tracks"] = boxes["host"] == boxes["device"]
+    a, b = probs.get("host"), probs.get("device")
+    r["prob_diff"] = float(np.abs(a - b).max()) if a is not None and b is not None and a.shape == b.shape else None
+    r["resample_speedup_events"] = round(min(r["host_resample_s"]) * 1e3 / min(r["device_resample_ms"]), 1)
+    r["resample_speedup_wall"] = round(min(r["host_resample_s"]) / min(r["device_resample_wall_s"]), 1)
+    r["whole_speedup"] = round(min(r["host_whole_s"]) / min(r["device_whole_s"]), 2)
+    print(json.dumps(r), flush=True)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--seconds", type=int, nargs="+", default=[60, 600])
     ap.add_argument("--batch-size", type=int, default=1024)
     ap.add_argument("--filter-freqs", action="store_true", help="measure the band-pass of the tracks instead")
+    ap.add_argument("--rate", type=int, default=SR, metavar="HZ",
+                    help="generate the recording at HZ and measure its resampling to 48 kHz instead")
     a = ap.parse_args(argv)
     import identifytracks as it
     import predict
@@ -173,6 +284,12 @@ def main(argv=None):
     for windows in ("host", "device"):  # warm-up: kernels loaded, plans made, allocator filled
         p.predict_tracks(synthetic(10), rng=np.random.RandomState(0), detector="gpu", windows=windows,
                          batch_size=a.batch_size, filter_freqs=a.filter_freqs)
+    if a.rate != SR:
+        fe.resample_poly(torch.zeros(1000, dtype=torch.int16, device=device), a.rate)  # warm-up: kernel loaded, taps up
+        with tempfile.TemporaryDirectory() as tmp:
+            for seconds in a.seconds:
+                resample_report(p, predict, fe, it, seconds, a.rate, a.batch_size, tmp)
+        return
     for seconds in a.seconds:
         x = synthetic(seconds)
         if a.filter_freqs:

@@ -25,18 +25,18 @@ import torch  # noqa: E402
 SR = 48000
 
 
-def synthetic(seconds, seed=0):
-    """White noise + three 0.5-1.5 s chirps in every 10 s, float32."""
+def synthetic(seconds, seed=0, sr=SR):
+    """White noise + three 0.5-1.5 s chirps in every 10 s, float32, sampled at sr."""
     rng = np.random.default_rng(seed)
-    n = SR * seconds
+    n = sr * seconds
     x = rng.normal(0, 0.003, n).astype(np.float32)
     for block in range(0, seconds, 10):
         for _ in range(3):
             dur = rng.uniform(0.5, 1.5)
             on = block + rng.uniform(0, min(10, seconds - block) - dur)
             f0, f1 = rng.uniform(800, 9000, 2)
-            a, b = int(on * SR), int((on + dur) * SR)
-            tt = np.arange(b - a) / SR
+            a, b = int(on * sr), int((on + dur) * sr)
+            tt = np.arange(b - a) / sr
             x[a:b] += (0.3 * np.sin(2 * np.pi * (f0 * tt + 0.5 * (f1 - f0) / dur * tt * tt))).astype(np.float32)
     return x
 
