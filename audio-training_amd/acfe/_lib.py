@@ -139,10 +139,12 @@ SIGNATURES: dict[str, list] = {
     "acfe_sosfilt_workspace": [I64, I32],
     "acfe_sosfilt_segments": [P, I64, P, P, I32, P, I64, P, P],
     "acfe_resample_poly": [P, I32, I64, P, I32, I32, I32, I64, P, I64, P],
+    "acfe_pcen_segments_workspace": [I32, I64],
+    "acfe_pcen_normalize_segments": [P, I32, I64, P, I32, P, I32, P, P, P],
 }
 _RESTYPES = {"acfe_last_error": C.c_char_p, "acfe_conv2d_wgrad_workspace": I64, "acfe_conv2d_dgrad_workspace": I64, "acfe_crc32c": C.c_uint32,
              "acfe_c1bn_workspace": I64, "acfe_stft_mag_workspace": I64, "acfe_morph_box_workspace": I64,
-             "acfe_sosfilt_workspace": I64}
+             "acfe_sosfilt_workspace": I64, "acfe_pcen_segments_workspace": I64}
 
 PAD_END, PAD_CENTER_CONSTANT, PAD_CENTER_REFLECT = 0, 1, 2
 LAYOUT_BTM, LAYOUT_BMT = 0, 1

@@ -313,10 +313,76 @@ class _PCENFunction(torch.autograd.Function):
         return None, dparams, None, None, None
 
 
+def check_pcen_segments(seg_start, batch: int) -> np.ndarray:
+    """A segment table of acfe_pcen_normalize_segments (predict.pcen_segments'
+    form) as contiguous int32, after checking it against a launch of `batch`
+    clips: ValueError unless it is 1-D with at least 2 entries, starts at 0,
+    never decreases and ends at batch.  Segment s is the clips
+    [seg_start[s], seg_start[s + 1]); an empty segment is allowed."""
+    seg = np.asarray(seg_start)
+    if seg.ndim != 1 or len(seg) < 2:
+        raise ValueError(f"segment table must be 1-D with at least 2 offsets, got shape {seg.shape}")
+    if not np.issubdtype(seg.dtype, np.integer):
+        raise ValueError(f"segment table must hold integers, got {seg.dtype}")
+    seg = seg.astype(np.int64)
+    if seg[0] != 0 or seg[-1] != batch:
+        raise ValueError(f"segment table must run from 0 to the batch of {batch}, got {int(seg[0])} .. {int(seg[-1])}")
+    if (np.diff(seg) < 0).any():
+        k = int(np.flatnonzero(np.diff(seg) < 0)[0])
+        raise ValueError(f"segment table decreases at entry {k + 1}: {int(seg[k])} -> {int(seg[k + 1])}")
+    return np.ascontiguousarray(seg, np.int32)
+
+
+def pcen_normalize_segments(y_bmt: torch.Tensor, segments, out_dtype=torch.float32):
+    """normalize_minmax (tfpcen.py:105-110) of acfe_pcen_fwd's un-normalised
+    output y [B, M, T] per segment of the host table `segments`
+    (check_pcen_segments) -> (out [B, M, T] of out_dtype, seg_minmax
+    [n_seg, 2] fp32 {min, max}).  Each segment is normalised by the extrema of
+    its own clips, bit-identical to normalising those clips alone
+    (csrc/pcen_scope.hip)."""
+    require_cuda(y_bmt)
+    if y_bmt.dtype != torch.float32 or y_bmt.dim() != 3 or not y_bmt.is_contiguous():
+        raise TypeError("y must be a contiguous [B, M, T] float32 tensor")
+    b, clip = y_bmt.shape[0], y_bmt.shape[1] * y_bmt.shape[2]
+    seg = check_pcen_segments(segments, b)
+    n_seg = len(seg) - 1
+    if n_seg > b:
+        raise ValueError(f"{n_seg} segments for a batch of {b}: drop the empty ones")
+    dev = y_bmt.device
+    out = torch.empty(y_bmt.shape, dtype=out_dtype, device=dev)
+    seg_minmax = torch.empty((n_seg, 2), dtype=torch.float32, device=dev)
+    nbytes = lib.acfe_pcen_segments_workspace(b, clip)
+    _lib.check(nbytes, "acfe_pcen_segments_workspace")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    dseg = torch.from_numpy(seg).to(dev)
+    call("acfe_pcen_normalize_segments", ptr(y_bmt), b, clip, ptr(dseg), n_seg, ptr(out), dtype_code(out_dtype),
+         ptr(seg_minmax), ptr(ws), stream())
+    return out, seg_minmax
+
+
 def pcen(mel_btm: torch.Tensor, params: torch.Tensor, eps: float = 1e-6, out_dtype=torch.float32,
-         scope_minmax: torch.Tensor | None = None) -> torch.Tensor:
-    """tfpcen.PCEN.call + normalize_minmax: mel [B,T,M] -> normalised [B,M,T]."""
-    return _PCENFunction.apply(mel_btm.contiguous(), params, eps, out_dtype, scope_minmax)
+         scope_minmax: torch.Tensor | None = None, segments=None) -> torch.Tensor:
+    """tfpcen.PCEN.call + normalize_minmax: mel [B,T,M] -> normalised [B,M,T].
+    The min / max are those of the whole batch, or `scope_minmax` when given.
+    With `segments` (a host table of offsets, check_pcen_segments) every
+    segment of clips is normalised by its own extrema instead, as if it had
+    been a batch of its own; that form is inference only (no backward), and
+    excludes scope_minmax."""
+    if segments is None:
+        return _PCENFunction.apply(mel_btm.contiguous(), params, eps, out_dtype, scope_minmax)
+    if scope_minmax is not None:
+        raise ValueError("segments and scope_minmax exclude each other")
+    if torch.is_grad_enabled() and params.requires_grad:
+        raise RuntimeError("PCEN with segments is inference only: run it under torch.no_grad()")
+    mel_btm = mel_btm.contiguous()
+    require_cuda(mel_btm, params)
+    b, t, m = mel_btm.shape
+    seg = check_pcen_segments(segments, b)  # before any launch
+    npart = lib.acfe_pcen_partials(b, m)
+    y = torch.empty((b, m, t), dtype=torch.float32, device=mel_btm.device)
+    part = torch.empty(2 * npart, dtype=torch.float32, device=mel_btm.device)
+    call("acfe_pcen_fwd", ptr(mel_btm), b, t, m, ptr(params), float(eps), ptr(y), ptr(part), stream())
+    return pcen_normalize_segments(y, seg, out_dtype)[0]
 
 
 class PCEN(torch.nn.Module):
@@ -332,5 +398,5 @@ class PCEN(torch.nn.Module):
         self.eps = eps
         self.out_dtype = out_dtype
 
-    def forward(self, mel_btm, scope_minmax=None):
-        return pcen(mel_btm, self.params, self.eps, self.out_dtype, scope_minmax)
+    def forward(self, mel_btm, scope_minmax=None, segments=None):
+        return pcen(mel_btm, self.params, self.eps, self.out_dtype, scope_minmax, segments)

@@ -27,7 +27,11 @@ class FrontEnd(nn.Module):
 
     With `pcen=True` the mel energies go through trainable PCEN +
     normalize_minmax (tfpcen.py:42-110); otherwise the mel power itself is
-    the feature, as in the reference's raw_to_mel output (tfdataset.py:2049-2053)."""
+    the feature, as in the reference's raw_to_mel output (tfdataset.py:2049-2053).
+    `segments` (forward, features, forward_windows; inference only) is the
+    host table of frontend.check_pcen_segments: PCEN's min / max are then
+    taken per segment of clips instead of over the batch.  Without PCEN it has
+    no effect."""
 
     def __init__(self, n_mels=128, n_fft=4096, hop=281, sr=48000, fmin=100, fmax=11000, break_freq=1000,
                  pcen=True, dtype=torch.bfloat16, device=None, weights=None, power=2):
@@ -41,7 +45,7 @@ class FrontEnd(nn.Module):
         self.dtype = dtype
         self.timer = None  # bench.py: list receiving ("mel", ev0, ev1)
 
-    def forward(self, x1, x2=None, lam=None, pad_mode="end", scope_minmax=None):
+    def forward(self, x1, x2=None, lam=None, pad_mode="end", scope_minmax=None, segments=None):
         st1 = fe.normalize_stats(x1)
         if x2 is not None:
             st2 = fe.normalize_stats(x2)
@@ -52,15 +56,15 @@ class FrontEnd(nn.Module):
         # Normalise once into a scratch clip (frames overlap ~14.6x, so
         # normalising on load inside the STFT repeats the divide per frame).
         src = fe.normalize_apply(src, st, out=src if src is not x1 else None)
-        return self.features(src, pad_mode, scope_minmax)
+        return self.features(src, pad_mode, scope_minmax, segments)
 
-    def features(self, src_normalised, pad_mode="end", scope_minmax=None):
+    def features(self, src_normalised, pad_mode="end", scope_minmax=None, segments=None):
         """The tail of forward: already normalised clips [B, N] fp32 (forward's
         scratch clip, or frontend.normalize_windows' output) -> model input."""
         if self.pcen is not None:
             mel = self.plan.mel(src_normalised, None, pad_mode=pad_mode, power=self.power, layout="btm",
                                 timer=self.timer)
-            return self.pcen(mel, scope_minmax)
+            return self.pcen(mel, scope_minmax, segments)
         mel = self.plan.mel(src_normalised, None, pad_mode=pad_mode, power=self.power, layout="bmt", timer=self.timer)
         return ops.cast(mel, self.dtype)
 
@@ -73,7 +77,8 @@ class FrontEnd(nn.Module):
             return self.pcen(self.plan.mel_from_spec(spec, power=1, layout="btm", timer=self.timer), scope_minmax)
         return ops.cast(self.plan.mel_from_spec(spec, power=1, layout="bmt", timer=self.timer), self.dtype)
 
-    def forward_windows(self, rec, first, count, n=144000, hop=72000, pad_mode="constant", scope_minmax=None):
+    def forward_windows(self, rec, first, count, n=144000, hop=72000, pad_mode="constant", scope_minmax=None,
+                        segments=None):
         """Features of `count` overlapping windows of one device recording `rec`
         (1-D fp32): window w covers rec[(first + w) * hop : ... + n].  The
         streaming predict path (predict_utils.load_samples :53-148 slides 3 s
@@ -83,7 +88,7 @@ class FrontEnd(nn.Module):
         if self.pcen is not None:
             mel = self.plan.mel(view, st, pad_mode=pad_mode, power=self.power, layout="btm", n=n, clip_stride=hop,
                                 batch=count, timer=self.timer)
-            return self.pcen(mel, scope_minmax)
+            return self.pcen(mel, scope_minmax, segments)
         mel = self.plan.mel(view, st, pad_mode=pad_mode, power=self.power, layout="bmt", n=n, clip_stride=hop,
                             batch=count, timer=self.timer)
         return ops.cast(mel, self.dtype)

@@ -4,6 +4,7 @@ predict_utils.py:9-239).
 
   python predict.py --file REC.wav CHECKPOINT_DIR [--stride 1] [--batch-size 1024] [--detector gpu]
                     [--windows device] [--filter-freqs | --filter-below HZ] [--resample device]
+                    [--pcen-scope {batch,track,window}]
 
 The recording is decoded on the host (WAV via scipy; the reference's ffmpeg /
 librosa loader is out of scope) and resampled to 48 kHz: with scipy's
@@ -49,8 +50,21 @@ still never passes through host memory.  Both are off by default.
 `stride` seconds are read in place by the fused front-end kernel; the
 per-recording result is the mean of the window probabilities.
 
-Note: PCEN (if the model was trained with it) normalises min/max over each
-window batch, as Keras predict does per batch.
+--pcen-scope: PCEN (if the model was trained with it) ends in
+normalize_minmax, which scales its output by the min / max of everything the
+layer is given at once (tfpcen.py:105-110).  Which windows that is:
+  batch  (default) each launch of up to --batch-size windows of the recording,
+         all tracks together: a track's features depend on --batch-size and on
+         what else the recording holds.
+  track  each track's own windows, in runs of at most 32: what the reference
+         computes, whose model.predict runs once per track (predict.py:887)
+         and is cut into batches of 32 by Keras.  Tracks are split at 6 s, so
+         in practice this is one min / max per track.  --mode tracks only.
+  window each window by itself: a window's features depend on nothing else.
+The launches keep their size under every scope (they are cut at segment
+boundaries, never inside one); the kernels of acfe_pcen_normalize_segments take
+the extrema per segment of a launch and normalise each segment as if it had
+been a launch of its own, bit for bit.
 """
 from __future__ import annotations
 
@@ -439,6 +453,64 @@ def check_sos_segments(seg, sos, rec_len, out_len):
     return seg, sos
 
 
+PCEN_SCOPES = ("batch", "track", "window")
+KERAS_BATCH = 32  # the batch_size default of keras.Model.predict (predict.py:887 passes none)
+
+
+def pcen_segments(counts, scope, keras_batch=KERAS_BATCH):
+    """The clips that share PCEN's min / max (tfpcen.normalize_minmax, :105-110)
+    under `scope`, for windows laid out track after track with counts[k]
+    windows of track k -> the table of offsets of
+    acfe.frontend.check_pcen_segments (int32 [n_seg + 1]: segment s is the
+    windows [seg[s], seg[s + 1])), or None.  "batch": None, the extrema of
+    each launch.  "window": one segment per window.  "track": for every track
+    with windows, consecutive runs of at most keras_batch of them -- the
+    batches Keras predict cuts model.predict(one track's windows) into
+    (predict.py:887), each of which the layer normalises by its own extrema."""
+    if scope not in PCEN_SCOPES:
+        raise ValueError(f"pcen scope {scope!r}: expected one of {PCEN_SCOPES}")
+    if scope == "batch":
+        return None
+    counts = [int(c) for c in counts]
+    if scope == "window":
+        return np.arange(sum(counts) + 1, dtype=np.int32)
+    if keras_batch < 1:
+        raise ValueError("keras_batch must be positive")
+    seg, at = [0], 0
+    for c in counts:
+        for a in range(0, c, keras_batch):
+            at += min(keras_batch, c - a)
+            seg.append(at)
+    return np.array(seg, np.int32)
+
+
+def segment_launches(n, batch_size, segments=None):
+    """The launches of n windows in order -> list of (a, b, table): windows
+    [a, b) with b - a <= batch_size.  Without `segments` they are chunks of
+    batch_size and table is None.  With a table of pcen_segments' form over
+    the n windows every launch is filled greedily with whole segments, so that
+    none is split, and `table` is the launch's own: rebased to start at 0,
+    without empty segments.  ValueError for a segment larger than
+    batch_size."""
+    if batch_size < 1:
+        raise ValueError("batch_size must be positive")
+    if segments is None:
+        return [(a, min(a + batch_size, n), None) for a in range(0, n, batch_size)]
+    from acfe.frontend import check_pcen_segments
+
+    seg = check_pcen_segments(segments, n).astype(np.int64)
+    seg = seg[np.concatenate(([True], np.diff(seg) > 0))]  # empty segments hold no window
+    if (np.diff(seg) > batch_size).any():
+        raise ValueError(f"a PCEN segment of {int(np.diff(seg).max())} windows does not fit a launch of "
+                         f"batch_size {batch_size}")
+    out, first = [], 0
+    for k in range(1, len(seg)):
+        if k + 1 == len(seg) or seg[k + 1] - seg[first] > batch_size:
+            out.append((int(seg[first]), int(seg[k]), (seg[first:k + 1] - seg[first]).astype(np.int32)))
+            first = k
+    return out
+
+
 def host_frames(frames):
     """A recording as numpy: a 1-D float32 device tensor is downloaded, numpy
     input passes through."""
@@ -515,12 +587,17 @@ class Predictor:
         self._detector = None  # acfe.tracks.SignalDetector of predict_tracks(detector="gpu")
 
     @torch.no_grad()
-    def predict_windows(self, recording, stride=1.0, batch_size=1024, pad_mode="constant"):
+    def predict_windows(self, recording, stride=1.0, batch_size=1024, pad_mode="constant", pcen_scope="batch"):
         """Sigmoid outputs [n_windows, classes] for 3 s windows every `stride` s
         of a numpy recording, or of a 1-D float32 device tensor, which is read
-        where it lies."""
+        where it lies.  pcen_scope "batch" normalises PCEN over each launch of
+        batch_size windows, "window" over every window by itself, so that a
+        window's output depends on nothing else; there are no tracks here, so
+        "track" is a ValueError."""
         from acfe import ops
 
+        if pcen_scope not in ("batch", "window"):
+            raise ValueError(f"pcen scope {pcen_scope!r}: expected 'batch' or 'window' for windows without tracks")
         n = SR * 3
         if isinstance(recording, torch.Tensor):
             if recording.dim() != 1 or recording.dtype != torch.float32:
@@ -538,40 +615,45 @@ class Predictor:
         out = []
         for first in range(0, n_win, batch_size):
             cnt = min(batch_size, n_win - first)
-            feats = self.frontend.forward_windows(dev_rec, first, cnt, n=n, hop=hop, pad_mode=pad_mode)
+            segs = np.arange(cnt + 1, dtype=np.int32) if pcen_scope == "window" else None
+            feats = self.frontend.forward_windows(dev_rec, first, cnt, n=n, hop=hop, pad_mode=pad_mode, segments=segs)
             out.append(ops.sigmoid(self.model(feats)))
         return torch.cat(out).float().cpu().numpy()
 
     @torch.no_grad()
-    def predict_clips(self, clips: np.ndarray, batch_size=1024):
+    def predict_clips(self, clips: np.ndarray, batch_size=1024, segments=None):
         """Sigmoid outputs [B, classes] for raw [B, 144000] windows (each
-        normalised on the GPU, centred STFT with constant padding)."""
+        normalised on the GPU, centred STFT with constant padding).  segments:
+        a table of pcen_segments' form over the B windows; PCEN then normalises
+        every segment by its own extrema, and the launches are cut at segment
+        boundaries (segment_launches).  None: the extrema of each launch."""
         from acfe import ops
 
         out = []
-        for a in range(0, len(clips), batch_size):
-            x = torch.from_numpy(np.ascontiguousarray(clips[a:a + batch_size], np.float32)).to(self.device)
-            out.append(ops.sigmoid(self.model(self.frontend(x, pad_mode="constant"))))
+        for a, b, seg in segment_launches(len(clips), batch_size, segments):
+            x = torch.from_numpy(np.ascontiguousarray(clips[a:b], np.float32)).to(self.device)
+            out.append(ops.sigmoid(self.model(self.frontend(x, pad_mode="constant", segments=seg))))
         return torch.cat(out).float().cpu().numpy()
 
     @torch.no_grad()
-    def predict_plan(self, rec: torch.Tensor, plan: np.ndarray, batch_size=1024):
+    def predict_plan(self, rec: torch.Tensor, plan: np.ndarray, batch_size=1024, segments=None):
         """predict_clips for windows that stay on the device: sigmoid outputs
         [n_windows, classes] for the windows the table `plan`
         (track_window_plan) cuts from the 1-D fp32 device recording `rec`,
-        cut and normalised by one kernel per chunk of batch_size windows."""
+        cut and normalised by one kernel per launch of up to batch_size
+        windows; segments as in predict_clips."""
         from acfe import frontend as fe
         from acfe import ops
 
         n = SR * 3
         out = []
-        for a in range(0, len(plan), batch_size):
-            x = fe.normalize_windows(rec, plan[a:a + batch_size], n)
-            out.append(ops.sigmoid(self.model(self.frontend.features(x, pad_mode="constant"))))
+        for a, b, seg in segment_launches(len(plan), batch_size, segments):
+            x = fe.normalize_windows(rec, plan[a:b], n)
+            out.append(ops.sigmoid(self.model(self.frontend.features(x, pad_mode="constant", segments=seg))))
         return torch.cat(out).float().cpu().numpy()
 
     def predict_tracks(self, frames, threshold=None, batch_size=1024, rng=None, detector="host", windows="host",
-                       filter_freqs=False, filter_below=None):
+                       filter_freqs=False, filter_below=None, pcen_scope="batch"):
         """Tracks of one recording with their ModelResult (predict.py:735-956);
         `detector` as in detect_tracks ("gpu" keeps one SignalDetector per Predictor).
         windows "host" cuts every window with numpy and uploads them; "device"
@@ -586,9 +668,20 @@ class Predictor:
         `frames` may be a 1-D float32 device tensor
         (load_recording(resample="device")): with detector "gpu" and windows
         "device" its samples never visit the host; with a host detector or
-        host windows it is downloaded once and the call goes on as for numpy."""
+        host windows it is downloaded once and the call goes on as for numpy.
+        pcen_scope: which windows share PCEN's min / max (pcen_segments):
+        "batch" every launch of batch_size windows of the recording, "track"
+        each track's own windows in runs of 32, as the reference's
+        model.predict per track normalises them, "window" each window alone.
+        Under "track" and "window" a track's result does not depend on
+        batch_size or on the other tracks; "track" needs batch_size >= 32."""
         if windows not in ("host", "device"):
             raise ValueError(f"windows {windows!r}: expected 'host' or 'device'")
+        if pcen_scope not in PCEN_SCOPES:
+            raise ValueError(f"pcen scope {pcen_scope!r}: expected one of {PCEN_SCOPES}")
+        if pcen_scope == "track" and batch_size < KERAS_BATCH:
+            raise ValueError(f"pcen scope 'track' normalises runs of up to {KERAS_BATCH} windows together: "
+                             f"batch_size {batch_size} is too small")
         if isinstance(frames, torch.Tensor) and (detector == "host" or windows == "host"):
             frames = host_frames(frames)
         if detector == "gpu":
@@ -605,7 +698,8 @@ class Predictor:
         if windows == "host":
             wins = track_windows(frames, SR, tracks, rng=rng, filter_freqs=filter_freqs, filter_below=filter_below)
             counts = [len(w) for w in wins]
-            probs = self.predict_clips(np.concatenate(wins), batch_size) if sum(counts) else None
+            probs = self.predict_clips(np.concatenate(wins), batch_size,
+                                       pcen_segments(counts, pcen_scope)) if sum(counts) else None
         else:
             plan, counts, segs = track_window_plan(len(frames), SR, tracks, rng=rng, segments=True)
             rec = dev[0] if dev else torch.from_numpy(np.ascontiguousarray(frames)).to(self.device)
@@ -615,7 +709,7 @@ class Predictor:
                 seg, sos, plan2 = sos_segment_plan(tracks, segs, plan, counts, SR, filter_freqs, filter_below)
                 if (sos != SOS_IDENTITY).any():
                     rec, plan = fe.sosfilt_segments(rec, seg, sos), plan2
-            probs = self.predict_plan(rec, plan, batch_size) if len(plan) else None
+            probs = self.predict_plan(rec, plan, batch_size, pcen_segments(counts, pcen_scope)) if len(plan) else None
         at = 0
         for t, c in zip(tracks, counts):
             if c == 0:
@@ -636,8 +730,9 @@ class Predictor:
                 r.raw_confidence = round(float(max_p[1]) * 100)
         return tracks, end
 
-    def predict_file(self, path, stride=1.0, batch_size=1024, threshold=0.7, resample="host"):
-        probs = self.predict_windows(load_recording(path, resample=resample, device=self.device), stride, batch_size)
+    def predict_file(self, path, stride=1.0, batch_size=1024, threshold=0.7, resample="host", pcen_scope="batch"):
+        probs = self.predict_windows(load_recording(path, resample=resample, device=self.device), stride, batch_size,
+                                     pcen_scope=pcen_scope)
         mean = probs.mean(0)
         labels = [(self.labels[i], float(mean[i])) for i in np.argsort(-mean) if mean[i] >= threshold]
         return {"file": str(path), "windows": int(probs.shape[0]), "labels": labels,
@@ -664,17 +759,24 @@ def main(argv=None):
     ap.add_argument("--resample", choices=("host", "device"), default="host",
                     help="resampling of a recording that is not at 48 kHz: scipy's resample_poly on the host, or the "
                          "same filter as a HIP kernel on the uploaded samples (the recording then stays on the GPU)")
+    ap.add_argument("--pcen-scope", choices=PCEN_SCOPES, default="batch",
+                    help="the windows that share PCEN's min / max: every launch of --batch-size windows, each "
+                         "track's own windows in runs of 32 as the reference's model.predict per track "
+                         "(--mode tracks only), or each window alone")
     a = ap.parse_args(argv)
+    if a.mode == "windows" and a.pcen_scope == "track":
+        ap.error("--pcen-scope track needs --mode tracks: --mode windows has no tracks")
     p = Predictor(a.model)
     for f in a.file:
         t0 = time.perf_counter()
         if a.mode == "tracks":
             rec = load_recording(f, resample=a.resample, device=p.device)
             tracks, end = p.predict_tracks(rec, a.threshold, a.batch_size, detector=a.detector, windows=a.windows,
-                                           filter_freqs=a.filter_freqs, filter_below=a.filter_below)
+                                           filter_freqs=a.filter_freqs, filter_below=a.filter_below,
+                                           pcen_scope=a.pcen_scope)
             r = {"file": str(f), "end": end, "tracks": [t.get_meta() for t in tracks]}
         else:
-            r = p.predict_file(f, a.stride, a.batch_size, a.threshold, resample=a.resample)
+            r = p.predict_file(f, a.stride, a.batch_size, a.threshold, resample=a.resample, pcen_scope=a.pcen_scope)
         r["seconds"] = round(time.perf_counter() - t0, 3)
         print(json.dumps(r, default=float))
 

@@ -38,6 +38,9 @@
  *   acfe_windows_normalize predict_utils.py:59-160   load_samples' window cut + normalize_data
  *   acfe_sosfilt_segments  predict_utils.py:103-113, 245-262  load_samples' Butterworth band-pass (sosfilt)
  *   acfe_resample_poly     predict.py:59-66          load_recording's resampling to 48 kHz (as resample_poly)
+ *   acfe_pcen_segments_workspace, acfe_pcen_normalize_segments
+ *                          tfpcen.py:105-110, predict.py:887  normalize_minmax as Keras predict batches it:
+ *                                                    per track (in batches of 32) instead of per launch
  */
 #ifndef ACFE_H
 #define ACFE_H
@@ -749,6 +752,31 @@ int acfe_sosfilt_segments(const float* rec, int64_t rec_len, const int64_t* seg,
  * and nothing outside out[0, n_out) is written. */
 int acfe_resample_poly(const void* x, int x_dtype, int64_t n_in, const float* h, int n_taps, int up, int down,
                        int64_t t0, float* out, int64_t n_out, void* stream);
+
+/* normalize_minmax (tfpcen.py:105-110) per segment of a launch
+ * (csrc/pcen_scope.hip).  The reference's predict path hands one track's
+ * windows to Keras predict (predict.py:887), which normalises each batch of
+ * 32 by its own extrema; here the windows of many tracks share a launch and
+ * a table says which clips belong together.  y_bmt is acfe_pcen_fwd's
+ * un-normalised output [batch][clip_elems] (clip_elems = M * T); seg_start is
+ * a device table of n_seg + 1 offsets, segment s being the clips
+ * [seg_start[s], seg_start[s + 1]).  For a clip b of segment s
+ *   out[b][i] = 2*((y[b][i] - mn_s)/(mx_s - mn_s)) - 1   (fp32 or bf16)
+ * with mn_s / mx_s the fminf / fmaxf fold over the segment's elements (NaNs
+ * ignored), bit-identical to acfe_pcen_normalize run on that segment's clips
+ * alone; seg_minmax[s] = {mn_s, mx_s}, {+inf, -inf} for an empty segment.
+ * ws: acfe_pcen_segments_workspace(batch, clip_elems) bytes (4-byte aligned).
+ * A valid table starts at 0, is non-decreasing and ends at batch; whatever
+ * it holds, nothing outside y, seg_start[0, n_seg], ws and
+ * out[0, batch * clip_elems) is read or written: the offsets are clamped to
+ * [0, batch], a range that runs backwards is empty, and a clip that no
+ * segment covers is normalised with {+inf, -inf}.  ACFE_E_INVAL, before any
+ * launch, for a null pointer, batch <= 0, clip_elems <= 0, n_seg <= 0,
+ * n_seg > batch, a launch of more than 2^31 - 1 workgroups, or a dtype other
+ * than F32 / BF16 (the workspace call: for the sizes among these). */
+int64_t acfe_pcen_segments_workspace(int batch, int64_t clip_elems);
+int acfe_pcen_normalize_segments(const float* y_bmt, int batch, int64_t clip_elems, const int32_t* seg_start,
+                                 int n_seg, void* out, int out_dtype, float* seg_minmax, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

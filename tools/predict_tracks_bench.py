@@ -56,7 +56,26 @@ generated at HZ and written as an int16 mono WAV; one JSON line per length:
                      ((K + 3) 2^-24 sum |h x| + ...), from the first 2^20 outputs
   tracks, same_tracks, prob_diff   of the two whole calls
 
+--pcen-scope measures PCEN's min / max per track (predict_tracks(pcen_scope=
+"track")) against per launch ("batch") instead, detector "gpu" and windows
+"device"; one JSON line per length:
+
+  whole_s            the whole call under either scope, alternating, after one
+                     untimed pair at this length
+  tracks_changed     tracks whose ModelResult (labels, confidences, raw tag)
+                     differs between the scopes; labels_changed: those whose
+                     labels or raw tag differ, not only a confidence
+  windows, segments, launches   of the "track" table (segment_launches)
+  normalise_ms       HIP events around the normalise stage over the launches'
+                     un-normalised PCEN output (y_bytes of float32, computed
+                     beforehand): batch = acfe_pcen_normalize (one kernel);
+                     track = frontend.pcen_normalize_segments (table upload,
+                     workspace, three kernels).  One untimed run of each, then
+                     STAGE_REPS timed, alternating; normalise_extra_ms is the
+                     difference of the minima
+
   python tools/predict_tracks_bench.py [--seconds 60 600] [--batch-size 1024] [--filter-freqs] [--rate HZ]
+                                       [--pcen-scope]
 """
 from __future__ import annotations
 
@@ -264,6 +283,75 @@ def resample_report(p, predict, fe, it, seconds, rate, batch_size, tmp):
     print(json.dumps(r), flush=True)
 
 
+def scope_report(p, predict, fe, it, x, seconds, batch_size):
+    from acfe._lib import call, lib
+    from acfe._torch import ptr, stream
+
+    r = {"seconds": seconds, "gpu": torch.cuda.get_device_name(0), "batch_size": batch_size, "pcen_scope": True}
+    whole = {"batch": [], "track": []}
+    results = {}
+    for k in range(WHOLE_REPS + 1):
+        for scope in ("batch", "track"):
+            it.Signal._next_id = 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            tracks, end = p.predict_tracks(x, rng=np.random.RandomState(0), detector="gpu", windows="device",
+                                           batch_size=batch_size, pcen_scope=scope)
+            torch.cuda.synchronize()
+            if k:  # the first pair is the warm-up of this length
+                whole[scope].append(round(time.perf_counter() - t0, 4))
+            results[scope] = [[q.get_meta() for q in t.predictions] for t in tracks]
+    r["batch_whole_s"], r["track_whole_s"] = whole["batch"], whole["track"]
+    r["tracks"] = len(results["batch"])
+    r["tracks_changed"] = sum(a != b for a, b in zip(results["batch"], results["track"]))
+    r["labels_changed"] = sum([(q["species"], q.get("raw_tag")) for q in a] != [(q["species"], q.get("raw_tag")) for q in b]
+                              for a, b in zip(results["batch"], results["track"]))
+
+    dev = []
+    tracks, frames, end = predict.detect_tracks(x, detector=p._detector, dev_out=dev)
+    plan, counts = predict.track_window_plan(len(frames), SR, tracks, rng=np.random.RandomState(0))
+    seg = predict.pcen_segments(counts, "track")
+    r["windows"], r["segments"] = len(plan), len(seg) - 1
+    launches = predict.segment_launches(len(plan), batch_size, seg)
+    r["launches"] = [b - a for a, b, _ in launches]
+    ys = []
+    with torch.no_grad():
+        for a, b, table in launches:
+            w = fe.normalize_windows(dev[0], plan[a:b], N)
+            mel = p.frontend.plan.mel(w, None, pad_mode="constant", power=p.frontend.power, layout="btm")
+            bb, t, m = mel.shape
+            npart = lib.acfe_pcen_partials(bb, m)
+            y = torch.empty((bb, m, t), dtype=torch.float32, device=mel.device)
+            part = torch.empty(2 * npart, dtype=torch.float32, device=mel.device)
+            call("acfe_pcen_fwd", ptr(mel), bb, t, m, ptr(p.frontend.pcen.params), 1e-6, ptr(y), ptr(part), stream())
+            ys.append((y, part, npart, table))
+    r["y_bytes"] = sum(y.numel() * 4 for y, _, _, _ in ys)
+    dt = p.frontend.dtype
+
+    def norm_batch():
+        for y, part, npart, _ in ys:
+            out = torch.empty(y.shape, dtype=dt, device=y.device)
+            stats = torch.empty(4, dtype=torch.float32, device=y.device)
+            call("acfe_pcen_normalize", ptr(y), y.numel(), ptr(part), npart, None, ptr(out), 1, ptr(stats), stream())
+
+    def norm_track():
+        for y, _, _, table in ys:
+            fe.pcen_normalize_segments(y, table, dt)
+
+    for k in range(STAGE_REPS + 1):
+        for name, fn in (("batch", norm_batch), ("track", norm_track)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if k:  # the first run of each is not counted
+                r.setdefault(f"{name}_normalise_ms", []).append(round(e0.elapsed_time(e1), 4))
+    r["normalise_extra_ms"] = round(min(r["track_normalise_ms"]) - min(r["batch_normalise_ms"]), 4)
+    r["whole_ratio"] = round(min(r["track_whole_s"]) / min(r["batch_whole_s"]), 3)
+    print(json.dumps(r), flush=True)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--seconds", type=int, nargs="+", default=[60, 600])
@@ -271,6 +359,8 @@ def main(argv=None):
     ap.add_argument("--filter-freqs", action="store_true", help="measure the band-pass of the tracks instead")
     ap.add_argument("--rate", type=int, default=SR, metavar="HZ",
                     help="generate the recording at HZ and measure its resampling to 48 kHz instead")
+    ap.add_argument("--pcen-scope", action="store_true",
+                    help="measure PCEN's min / max per track (pcen_scope='track') against per launch instead")
     a = ap.parse_args(argv)
     import identifytracks as it
     import predict
@@ -294,6 +384,9 @@ def main(argv=None):
         x = synthetic(seconds)
         if a.filter_freqs:
             filter_report(p, predict, fe, it, x, seconds, a.batch_size)
+            continue
+        if a.pcen_scope:
+            scope_report(p, predict, fe, it, x, seconds, a.batch_size)
             continue
         r = {"seconds": seconds, "gpu": torch.cuda.get_device_name(0), "batch_size": a.batch_size}
         metas = {}
