@@ -126,6 +126,7 @@ SIGNATURES: dict[str, list] = {
     "acfe_dense_fwd": [P, P, P, I32, I32, I32, P, P],
     "acfe_dense_bwd": [P, P, P, I32, I32, I32, P, P, P, P],
     "acfe_loss": [P, P, I32, I32, I32, F32, P, P, P, P],
+    "acfe_loss_weighted": [P, P, I32, I32, I32, F32, P, F32, P, P, P, P, P],
     "acfe_adam_step": [P, P, P, P, I64, F32, F32, F32, F32, F32, P],
     "acfe_stft_mag_workspace": [I64, I32, I32],
     "acfe_stft_mag": [P, I64, I32, I32, P, P, P, P],

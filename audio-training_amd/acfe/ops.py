@@ -1667,15 +1667,29 @@ def sigmoid(z: torch.Tensor) -> torch.Tensor:
 LOSS_MODES = {"bce": 0, "binary": 0, "cce": 1, "categorical": 1}
 
 
-def loss_and_grad(logits: torch.Tensor, target: torch.Tensor, mode: str = "cce", grad_scale: float | None = None):
+def loss_and_grad(logits: torch.Tensor, target: torch.Tensor, mode: str = "cce", grad_scale: float | None = None,
+                  class_weights: torch.Tensor | None = None, label_smoothing: float = 0.0):
     """Keras loss (audiomodel.loss, :1206-1223) on sigmoid(logits): returns
     (loss[1] fp32 device tensor, dL/dlogits).  grad_scale defaults to 1/B
-    (the batch mean)."""
+    (the batch mean).
+
+    class_weights (1-D fp32 tensor of length L on the logits' device, finite
+    and >= 0 by the caller's check) weighs each row by the weight of its
+    target's argmax class, as Keras fit(class_weight=...) does (audiomodel.py
+    :523-562); label_smoothing is that of the loss object (:1206-1223).  The
+    loss stays the sum over the batch divided by B.  With both at their
+    defaults the call is acfe_loss; otherwise acfe_loss_weighted (its
+    launcher is acfe/loss.py), still two launches and no host
+    synchronisation."""
     B, L = logits.shape
+    gs = 1.0 / B if grad_scale is None else grad_scale
+    if class_weights is not None or label_smoothing != 0.0:
+        from .loss import weighted_loss_and_grad
+
+        return weighted_loss_and_grad(logits, target, LOSS_MODES[mode], gs, class_weights, label_smoothing)
     loss = _empty((1,), F32, logits.device)
     dz = torch.empty_like(logits)
     ws = _empty((B,), F32, logits.device)
-    gs = 1.0 / B if grad_scale is None else grad_scale
     call("acfe_loss", ptr(logits.contiguous()), ptr(target.contiguous().to(F32)), B, L, LOSS_MODES[mode], gs, ptr(loss),
          ptr(dz), ptr(ws), stream())
     return loss, dz

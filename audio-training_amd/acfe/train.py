@@ -11,6 +11,7 @@ torch.distributed.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -106,9 +107,27 @@ class Trainer:
     Keras-Adam; `step` runs one full training iteration on device tensors."""
 
     def __init__(self, model: nn.Module, frontend: FrontEnd, lr=0.01, loss="cce", process_group=None,
-                 device=None, bucket_bytes=dp.BUCKET_BYTES, pack_once=True):
+                 device=None, bucket_bytes=dp.BUCKET_BYTES, pack_once=True, class_weights=None, label_smoothing=0.0):
+        """class_weights: one weight per class (a sequence or array of floats,
+        finite and >= 0), Keras fit(class_weight=...) of audiomodel.py:523-562:
+        every example's loss and gradient are multiplied by the weight of its
+        target's argmax class, and `step` returns the weighted loss, as Keras
+        reports it.  label_smoothing: that of the Keras loss (:1206-1223), in
+        [0, 1).  With both at their defaults the step is unchanged."""
         self.model, self.frontend, self.loss_mode = model, frontend, loss
         self.device = device or next(model.parameters()).device
+        self.label_smoothing = float(label_smoothing)
+        if not 0.0 <= self.label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
+        self.class_weights = None
+        if class_weights is not None:
+            w = np.asarray(class_weights, dtype=np.float32)
+            classes = getattr(model, "classes", None)
+            if w.ndim != 1 or (classes is not None and w.shape[0] != classes):
+                raise ValueError(f"class_weights must be one weight per class ({classes}), got shape {w.shape}")
+            if not np.isfinite(w).all() or (w < 0).any():
+                raise ValueError("class_weights must be finite and >= 0")
+            self.class_weights = torch.from_numpy(w).to(self.device)  # uploaded once
         self.holder = nn.ModuleList([frontend, model])
         self.arena = ParamArena(self.holder, self.device)
         self.opt = Adam(self.arena, lr=lr)
@@ -147,7 +166,8 @@ class Trainer:
         try:
             feats = self.frontend.forward_spec(x1) if x1.dim() == 3 else self.frontend(x1, x2, lam)
             z = self.model(feats)
-            loss, dz = ops.loss_and_grad(z, y, self.loss_mode)
+            loss, dz = ops.loss_and_grad(z, y, self.loss_mode, class_weights=self.class_weights,
+                                         label_smoothing=self.label_smoothing)
             self.arena.zero_grad()
             if self.buckets is None:
                 z.backward(dz)

@@ -12,7 +12,19 @@ TFRecord shards.  The reference flow (load_datasets -> build_model -> compile
 (raw audio batches, mix_up pairs when augmenting) -> acfe.train.FrontEnd (GPU
 normalize / mix_up / STFT / mel / PCEN) + resnet WRResNet -> acfe.train.Trainer
 (loss, backward, RCCL all-reduce, Adam) -> checkpoints/<run>/ {model.pt,
-metadata.txt}.  Dataset curation options of the reference (taxonomy remaps,
+metadata.txt}.
+
+--use-weighting is the reference's option of that name (audiomodel.py:2299,
+:523-562): model.fit(class_weight=get_weighting(train, labels)).  The weights
+come from the training set's examples per label (tfdataset.get_weighting,
+reference tfdataset.py:1721-1761): (1 / n_label) * (n_total / number of labels
+with examples), clipped to [0.25, 4], and 0 for a label without examples.  Each
+training example's loss and gradient are multiplied by the weight of its
+label inside the loss kernel (acfe_loss_weighted); the reported training loss
+is the weighted one, as Keras's, and val_loss stays unweighted.
+--label-smoothing S is the label_smoothing of the loss object (:1206-1223).
+
+Dataset curation options of the reference (taxonomy remaps,
 cross-fold, rf/embeddings models) are out of scope.
 """
 from __future__ import annotations
@@ -89,7 +101,9 @@ def evaluate(trainer, dataset, multi_label, group=None):
         for x, y in dp.synced_batches(dataset, group=group):
             f = trainer.frontend.forward_spec(x) if x.dim() == 3 else trainer.frontend(x)
             z = trainer.model(f)
-            loss, _ = ops.loss_and_grad(z, y, trainer.loss_mode)
+            # the loss object's label smoothing applies to val_loss too; the class
+            # weights do not (Keras applies class_weight to training batches only)
+            loss, _ = ops.loss_and_grad(z, y, trainer.loss_mode, label_smoothing=trainer.label_smoothing)
             vm.update(z, y, loss)
     trainer.holder.train()
     logs = vm.result(torch.tensor(dp.allreduce_sums(vm.totals().tolist(), device=dev), dtype=torch.float64))
@@ -192,15 +206,6 @@ def train_model(args):
     torch.manual_seed(args.seed + rank)  # per-replica mix_up lambdas after the shared init
     frontend = FrontEnd(n_mels=n_mels, n_fft=n_fft, hop=281, fmin=fmin, fmax=fmax, break_freq=brk,
                         pcen=args.pcen, dtype=dtype, device=dev).to(dev)
-    trainer = Trainer(model, frontend, lr=args.lr, loss="bce" if args.multi_label else "cce", device=dev)
-    if args.weights:
-        if str(args.weights).endswith((".h5", ".keras")):  # reference checkpoints (audiomodel.py:569-595)
-            from keras_weights import load_keras_weights
-
-            load_keras_weights(model, args.weights)
-        else:
-            sd = torch.load(args.weights, map_location="cpu", weights_only=True)
-            trainer.holder.load_state_dict(sd)
     files, rshard = shard_files(tfdataset._files(td / "train"), rank, world)
     load_raw = bool(args.load_raw)
     # tfdataset.get_dataset (audiomodel.py:1607-1621): this rank's share of the
@@ -209,6 +214,26 @@ def train_model(args):
         td / "train", labels, files=files, record_shard=rshard, batch_size=args.batch_size, shuffle=args.shuffle,
         augment=args.augment and load_raw, device=dev, drop_remainder=world > 1, seed=args.seed, load_raw=load_raw)
     logging.info("rank %d: %d training examples, %d batches per epoch", rank, epoch_size, len(train_ds))
+    class_weights = None
+    if args.use_weighting:
+        # get_weighting(self.train, self.labels) of audiomodel.py:524-526: the
+        # label counts of every rank's share (gathered by the pass that counted
+        # epoch_size) are added up, so all ranks hold the same weights
+        counts = dp.allreduce_sums(train_ds.label_counts().tolist(), device=dev)
+        class_weights = tfdataset.get_weighting(counts)
+        if rank == 0:
+            for lab, c, w in zip(labels, counts, class_weights):
+                logging.info("class weight %s: %d examples, weight %g", lab, c, w)
+    trainer = Trainer(model, frontend, lr=args.lr, loss="bce" if args.multi_label else "cce", device=dev,
+                      class_weights=class_weights, label_smoothing=args.label_smoothing)
+    if args.weights:
+        if str(args.weights).endswith((".h5", ".keras")):  # reference checkpoints (audiomodel.py:569-595)
+            from keras_weights import load_keras_weights
+
+            load_keras_weights(model, args.weights)
+        else:
+            sd = torch.load(args.weights, map_location="cpu", weights_only=True)
+            trainer.holder.load_state_dict(sd)
     val_dir = td / "validation"
     val_ds = None
     if val_dir.exists() and tfdataset._files(val_dir):
@@ -264,7 +289,10 @@ def train_model(args):
         meta_out.update(name=args.model_name, ebird_labels=labels, labels=labels, n_mels=n_mels, fmin=fmin,
                         fmax=fmax, n_fft=n_fft, break_freq=brk, hop_length=281, power=2 if load_raw else 1, pcen=args.pcen,
                         multi_label=args.multi_label, loss_fn="bce" if args.multi_label else "cce", load_raw=load_raw,
-                        dtype=args.dtype, training_date=str(time.time()), magv2=True)
+                        dtype=args.dtype, training_date=str(time.time()), magv2=True,
+                        use_weighting=bool(args.use_weighting),
+                        class_weights=None if class_weights is None else [float(w) for w in class_weights],
+                        label_smoothing=args.label_smoothing)
         save_checkpoint(out_dir, trainer, meta_out, history)
         print(json.dumps({"run": args.name, "epochs": len(history["loss"]), "final_loss": history["loss"][-1],
                           "val_loss": history["val_loss"][-1:] or None, "clips_per_s": history["clips_per_s"]}))
@@ -301,6 +329,14 @@ def parse_args(argv=None):
     p.add_argument("--steps-per-epoch", type=int, default=0)
     p.add_argument("--checkpoint-dir", default="checkpoints")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--use-weighting", default=0, action="count",
+                   help="weigh every training example by its class (audiomodel.py:2299, :523-562: Keras "
+                        "fit(class_weight=...)): the weights are tfdataset.get_weighting (:1721-1761) of the training "
+                        "set's examples per label, (1 / n_label) * (n_total / labels with examples) clipped to "
+                        "[0.25, 4], 0 for a label without examples; validation stays unweighted (count flag, "
+                        "default off)")
+    p.add_argument("--label-smoothing", type=float, default=0.0,
+                   help="label_smoothing of the Keras loss (audiomodel.py:1206-1223), in [0, 1)")
     return p.parse_args(argv)
 
 

@@ -194,6 +194,7 @@ class AudioDataset:
         self.buffer = buf
         self.pool_rows = buf + 2 * self.per_chunk
         self._epoch_size = epoch_size
+        self._label_counts = None  # int64 [len(labels)], from the counting pass
         self._pool = None
         self._dstage = None
         self._stage_buf = None
@@ -217,7 +218,7 @@ class AudioDataset:
         text = ctypes.create_string_buffer(_TEXT_CAP)
         cnt = ctypes.c_int64()
         scratch = np.empty(self.nfloats, np.float32)  # the NaN / Inf filter needs the values
-        n = 0
+        n = np.zeros(len(self.labels), np.int64)  # kept examples per label
         try:
             with tfr.ShardReader(path) as rd:
                 r = 0
@@ -231,8 +232,9 @@ class AudioDataset:
                     if self._keep(i, r):
                         fl = lib.acfe_example_audio(rec[0], rec[1], self.key, scratch.ctypes.data, self.nfloats,
                                                     text, _TEXT_CAP, ctypes.byref(cnt))
-                        if fl >= 0 and fl & 2 and self._label_of(text.value.decode(errors="replace")) is not None:
-                            n += 1
+                        lab = self._label_of(text.value.decode(errors="replace")) if fl >= 0 and fl & 2 else None
+                        if lab is not None:
+                            n[lab] += 1
                     r += 1
         except IOError as e:
             logging.warning("skipping unreadable shard %s: %s", path, e)
@@ -245,10 +247,27 @@ class AudioDataset:
         feature has the expected size and is finite (the filters of
         read_tfrecord / filter_nan_samples, tfdataset.py:297)."""
         if self._epoch_size is None:
-            stable = {f: i for i, f in enumerate(self.files)}
-            with ThreadPoolExecutor(min(self.threads, max(1, len(self.files)))) as ex:
-                self._epoch_size = sum(ex.map(lambda f: self._count_file(stable[f], f), self.files))
+            self._epoch_size = int(self._count_pass().sum())
         return self._epoch_size
+
+    def _count_pass(self):
+        """The one decode pass behind count() and label_counts()."""
+        if self._label_counts is None:
+            stable = {f: i for i, f in enumerate(self.files)}
+            total = np.zeros(len(self.labels), np.int64)
+            with ThreadPoolExecutor(min(self.threads, max(1, len(self.files)))) as ex:
+                for n in ex.map(lambda f: self._count_file(stable[f], f), self.files):
+                    total += n
+            self._label_counts = total
+        return self._label_counts
+
+    def label_counts(self) -> np.ndarray:
+        """Kept examples per label of this rank's share, int64 [len(labels)]
+        (the distribution the reference's get_weighting works from,
+        tfdataset.py:1721-1761), under the filters of count() and gathered in
+        the same decode pass: count() is their sum.  When epoch_size was given
+        by the caller that pass has not run yet and runs here, on first use."""
+        return self._count_pass().copy()
 
     def __len__(self):
         n = self.count()
@@ -615,6 +634,25 @@ class _SlotPool:
                 self.cv.wait(timeout=_POLL)
             out = [self.free.pop() for _ in range(n)]
             return out, self.ev
+
+
+def get_weighting(dist) -> np.ndarray:
+    """Class weights of the reference's get_weighting (tfdataset.py:1737-1758)
+    for a vector of examples per label: 0 for a label without examples, else
+    (1 / dist_i) * (total / nz) clipped to [0.25, 4], with total = sum(dist)
+    and nz the number of labels that have examples; float32 throughout, in
+    that order, as the reference (whose dist is np.float32).  Returns float32
+    [len(dist)]; an all-zero dist gives all-zero weights."""
+    dist = np.asarray(dist, dtype=np.float32)
+    total = np.float32(0)
+    for d in dist:  # the reference's running float32 sum, in label order
+        total = np.float32(total + d)
+    nz = np.float32(np.count_nonzero(dist > 0))
+    w = np.zeros(dist.shape, np.float32)
+    for i, d in enumerate(dist):
+        if d > 0:
+            w[i] = min(max((np.float32(1) / d) * (total / nz), np.float32(0.25)), np.float32(4))
+    return w
 
 
 def _files(dir):

@@ -571,6 +571,22 @@ int acfe_dense_bwd(const float* x, const float* w, const float* dz, int B, int I
                    float* db, void* stream);
 int acfe_loss(const float* z, const float* y, int B, int L, int mode, float grad_scale, float* loss, float* dz,
               float* workspace, void* stream);
+/* acfe_loss with Keras fit(class_weight=...) on one-hot targets and the loss
+ * object's label_smoothing (audiomodel.py:523-562, :1206-1223), in the same two
+ * launches (csrc/loss_weighted.hip).  Per row b:
+ *   w_b = class_weight[argmax_j y[b][j]] on the unsmoothed y (ties and an
+ *         all-zero row: the lowest index, as tf.argmax); 1 when class_weight
+ *         (float[L]) is NULL.  Written to row_weight[b] unless that is NULL.
+ *   y'  = y (1 - s) + 0.5 s (mode 0) or + s / L (mode 1), s = label_smoothing.
+ *   row_loss[b] = w_b * (acfe_loss's row loss on y'),  dz[b] = w_b * (its dz),
+ *   loss[0] = sum_b row_loss[b] / B  (sum_over_batch_size: B, not sum w).
+ * row_loss: float[B] (required), row_weight: float[B] or NULL.  With
+ * class_weight NULL or all 1.0f and s = 0, loss and dz are bit-identical to
+ * acfe_loss.  ACFE_E_INVAL: a NULL required pointer, mode not 0 / 1, B <= 0,
+ * L <= 0, s outside [0, 1) or NaN; nothing is launched then. */
+int acfe_loss_weighted(const float* z, const float* y, int B, int L, int mode, float grad_scale,
+                       const float* class_weight, float label_smoothing, float* loss, float* dz, float* row_loss,
+                       float* row_weight, void* stream);
 
 /* Adam (tf.keras.optimizers.Adam, audiomodel.py:1226-1240) over a flat fp32
  * parameter arena; alpha = lr*sqrt(1-b2^t)/(1-b1^t). */
