@@ -49,6 +49,7 @@ SIGNATURES: dict[str, list] = {
     "acfe_conv2d_fwd": [P, I32, I32, I32, I32, P, I32, I32, I32, I32, I32, I32, I32, I32, P, P, I32, P, P],
     "acfe_conv2d_fwd_dropout": [P, I32, I32, I32, I32, P, I32, I32, I32, I32, I32, I32, I32, I32, P, P, I32, P, F32,
                                 C.c_uint64, P],
+    "acfe_conv2d_fwd_info": [I32] * 15 + [P],
     "acfe_conv2d_dgrad": [P, I32, I32, I32, I32, P, I32, I32, I32, I32, I32, I32, I32, I32, P, I32, P, P],
     "acfe_conv2d_dgrad_workspace": [I32] * 13,
     "acfe_conv2d_dgrad_bn_rows": [I32] * 9,
@@ -56,6 +57,7 @@ SIGNATURES: dict[str, list] = {
                              I32, P, I32, P],
     "acfe_conv2d_wgrad_workspace": [I32, I32, I32, I32, I32, I32, I32, I32, I32],
     "acfe_conv2d_wgrad": [P, I32, I32, I32, I32, P, I32, I32, I32, I32, I32, I32, I32, I32, P, F32, I32, P, P],
+    "acfe_conv2d_wgrad_info": [I32] * 11 + [P],
     "acfe_conv_r64_enable": [I32],
     "acfe_mel_w5_frames": [I32],
     "acfe_conv2d_wgrad_bnbwd_rows": [I32] * 5,
@@ -198,6 +200,39 @@ def wgrad_halo_info(N, H, W, C, K, fold=False, unpool=False):
     if not lib.acfe_conv2d_wgrad_halo_info(N, H, W, C, K, int(fold), int(unpool), out):
         return None
     return dict(zip(HALO_FIELDS, out))
+
+
+# ACFE_FWD_* of include/acfe.h (value = index)
+FWD_LEAVES = (None, "1x1_reg", "c16", "cw", "narrow", "rows", "p", "g", "generic")
+FWD_FIELDS = ("leaf", "a", "b", "grid_x", "grid_y", "tiles")
+
+
+def conv2d_fwd_info(N, H, W, C, K, R, S, stride, pad_top, pad_left, P, Q, dtype=DTYPE_BF16, dropout=False,
+                    stats=True):
+    """acfe_conv2d_fwd_info as a dict of FWD_FIELDS (which kernel
+    acfe_conv2d_fwd[_dropout] launches for the geometry, host only; leaf as its
+    FWD_LEAVES name; 16-byte-aligned tensors assumed), or None on invalid
+    arguments."""
+    out = (I32 * 6)()
+    if lib.acfe_conv2d_fwd_info(N, H, W, C, K, R, S, stride, pad_top, pad_left, P, Q, dtype, int(dropout),
+                                int(stats), out) != 1:
+        return None
+    d = dict(zip(FWD_FIELDS, out))
+    d["leaf"] = FWD_LEAVES[d["leaf"]]
+    return d
+
+
+WGRAD_FIELDS = ("path", "bmw", "fast_d", "fast_x", "splits", "chunk", "tiles", "reduce")
+
+
+def conv2d_wgrad_info(N, H, W, C, K, R, S, stride, P, Q, dtype=DTYPE_BF16):
+    """acfe_conv2d_wgrad_info as a dict of WGRAD_FIELDS (which kernel
+    acfe_conv2d_wgrad launches, host only: path 0 generic split-K, 1 halo,
+    2 row halo -- these two fill `path` only), or None on invalid arguments."""
+    out = (I32 * 8)()
+    if lib.acfe_conv2d_wgrad_info(N, H, W, C, K, R, S, stride, P, Q, dtype, out) != 1:
+        return None
+    return dict(zip(WGRAD_FIELDS, out))
 
 
 # ACFE_NN_* of include/acfe.h, in order

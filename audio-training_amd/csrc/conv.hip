@@ -40,6 +40,12 @@ using namespace acfe;
 __device__ __attribute__((aligned(64))) uint4 g_zero_page[4];
 
 
+// A thread's partial sums of its rounded outputs (the statistics slab).  bf16
+// values (8-bit significands) add in fp32 with little or no rounding.  fp32
+// outputs are summed in double: 18 of them added in fp32 were up to 3e-6 off a
+// column sum that nearly cancels, against the 1e-6 the slab is held to
+// (tests/test_conv_paths_gpu.py)
+template <typename T> using StatAcc = typename std::conditional<sizeof(T) == 4, double, float>::type;
 template <typename T> struct TT;
 template <> struct TT<uint16_t> { static constexpr int GR = 8, BK = 64; };
 template <> struct TT<float> { static constexpr int GR = 4, BK = 32; };
@@ -207,7 +213,7 @@ k_conv_fwd(ConvGeom g, const T* __restrict__ X, const T* __restrict__ Wp, const 
       const int col = wn * TWN + fn * 16 + (lane & 15);
       const int gcn = n0 + col;
       const float bv = (bias && gcn < g.K) ? bias[gcn] : 0.f;
-      float t1 = 0.f, t2 = 0.f;
+      StatAcc<T> t1 = 0, t2 = 0;
 #pragma unroll
       for (int fm = 0; fm < FM; ++fm)
 #pragma unroll
@@ -220,7 +226,8 @@ k_conv_fwd(ConvGeom g, const T* __restrict__ X, const T* __restrict__ Wp, const 
           if (m0 + row < g.M) {
             const float f = to_f(tv);
             t1 += f;
-            t2 += f * f;
+            if constexpr (sizeof(T) == 2) t2 += f * f;
+            else t2 += __fmul_rn(f, f);  // (the square rounds to fp32 once: 2^-24 relative)
           }
         }
       if (stats) {
@@ -440,7 +447,7 @@ k_conv_fwd_g(ConvGeom g, const T* __restrict__ X, const T* __restrict__ Wp, cons
       const int col = wn * TWN + fn * 16 + (lane & 15);
       const int gcn = n0 + col;
       const float bv = (bias && gcn < g.K) ? bias[gcn] : 0.f;
-      float t1 = 0.f, t2 = 0.f;
+      StatAcc<T> t1 = 0, t2 = 0;
 #pragma unroll
       for (int fm = 0; fm < FM; ++fm)
 #pragma unroll
@@ -453,7 +460,8 @@ k_conv_fwd_g(ConvGeom g, const T* __restrict__ X, const T* __restrict__ Wp, cons
           if (m0 + row < g.M) {
             const float f = to_f(tv);
             t1 += f;
-            t2 += f * f;
+            if constexpr (sizeof(T) == 2) t2 += f * f;
+            else t2 += __fmul_rn(f, f);  // (the square rounds to fp32 once: 2^-24 relative)
           }
         }
       if (stats && !res) {
@@ -2771,8 +2779,11 @@ k_conv1x1_reg(ConvGeom g, const uint16_t* __restrict__ X, const uint16_t* __rest
     const int b0i = ((l16 >> 3) & 1) * (NV / 2) + ((l16 >> 2) & 1) * (NV / 4) + ((l16 >> 1) & 1) * (NV / 8) +
                     (l16 & 1) * (NV / 16);
     __syncthreads();
+    // (NKB = 1: 8 values, one left per lane after three steps, the fourth has
+    // nothing to halve -- the two lanes of a bit-0 pair hold the sums of
+    // different pixels for the same value, and both add theirs)
 #pragma unroll
-    for (int k = 0; k < NV / 16; ++k) {
+    for (int k = 0; k < (NV >= 16 ? NV / 16 : 1); ++k) {
       const int idx = b0i + k, st = idx / (NKB * 4), rm = idx - st * (NKB * 4);
       const int col = (rm >> 2) * 16 + q * 4 + (rm & 3);
       atomicAdd(&sstat[st * KB + col], (double)sv[k]);
@@ -3853,26 +3864,61 @@ static bool fwd_p_ok(const ConvGeom& g, int BN) {
   return g.C % 64 == 0 && g.K % BN == 0 && g.R * g.S <= 64 && g.R < 32 && g.M < (1ll << 31) && span < (1ll << 31);
 }
 
-// k_conv_fwd_p (RES: with the residual epilogue of acfe_conv2d_fwd_add), persistent:
-// one 512-thread workgroup per CU (256 CUs), a multiple of 8
+// k_conv_fwd_p's persistent grid: one 512-thread workgroup per CU (256 CUs)
+// over ny N tiles, a multiple of 8 from 64 up
+static void fwd_p_grid(const ConvGeom& g, int BN, int* gp, int* ny, int* tiles) {
+  *ny = g.Kp / BN;
+  *tiles = (int)((g.M + 255) / 256);
+  int p = 256 / *ny;
+  if (p > *tiles) p = *tiles;
+  if (p >= 64) p &= ~7;
+  *gp = p;
+}
+
+// k_conv_fwd_p (RES: with the residual epilogue of acfe_conv2d_fwd_add) on that grid
 template <int BN, bool RES>
 static int launch_fwd_p(const ConvGeom& g, const void* x, const void* wp, const float* bias, void* y, double* stats,
                         int srows, hipStream_t s, const char* what) {
-  const int ny = g.Kp / BN, tiles = (int)((g.M + 255) / 256);
-  int gp = 256 / ny;
-  if (gp > tiles) gp = tiles;
-  if (gp >= 64) gp &= ~7;
+  int gp, ny, tiles;
+  fwd_p_grid(g, BN, &gp, &ny, &tiles);
   hipLaunchKernelGGL((k_conv_fwd_p<BN, false, RES>), dim3(gp, ny), dim3(512), 0, s, g, (const uint16_t*)x,
                      (const uint16_t*)wp, bias, (uint16_t*)y, stats, tiles, srows);
   return launch_rc(what);
 }
 
+// ---- forward dispatch (acfe_conv2d_fwd[_dropout], the stride-1 dgrad): ONE
+// function of the geometry, fwd_pick, names the kernel ("leaf"), its template
+// choice and its grid; launch_fwd switches on the answer and the host-only
+// query acfe_conv2d_fwd_info returns it -- the decision is written once.
+enum : unsigned { FWD_AL_X16 = 1, FWD_AL_W16 = 2, FWD_AL_Y16 = 4, FWD_AL_Y8 = 8, FWD_AL_ALL = 15 };
+static unsigned fwd_align(const void* x, const void* wp, const void* y) {
+  return (((uintptr_t)x & 15) == 0 ? FWD_AL_X16 : 0u) | (((uintptr_t)wp & 15) == 0 ? FWD_AL_W16 : 0u) |
+         (((uintptr_t)y & 15) == 0 ? FWD_AL_Y16 : 0u) | (((uintptr_t)y & 7) == 0 ? FWD_AL_Y8 : 0u);
+}
+
 // k_conv3x3_cw's case: 3x3 stride-1 "same", 32 -> 128 / 16 -> 256 channels
 // (wr_resnet_bird's stage-2 / 3 branch2b), 32-bit element indices, 16-B rows
-static bool cw_ok(const ConvGeom& g, const void* x, const void* wp, const void* y) {
+static bool cw_ok(const ConvGeom& g, unsigned al) {
   return g.R == 3 && g.S == 3 && g.st == 1 && g.pt == 1 && g.pl == 1 && g.P == g.H && g.Q == g.W &&
          ((g.C == 32 && g.K == 128) || (g.C == 16 && g.K == 256 && g.Kdp >= 160)) && g.Kp == g.K && g.ldy == g.K &&
-         g.M * g.K < (1ll << 32) && ((uintptr_t)x & 15) == 0 && ((uintptr_t)wp & 15) == 0 && ((uintptr_t)y & 15) == 0;
+         g.M * g.K < (1ll << 32) && (al & FWD_AL_X16) && (al & FWD_AL_W16) && (al & FWD_AL_Y16);
+}
+// its tiles: 256 (K = 256: 128) pixels, 64 (32 for narrow images) wide; ok: its case with < 2^31 tiles
+struct CwPlan {
+  bool ok;
+  int segw, tiles_h, tiles_w;
+  long long nt;
+};
+static CwPlan cw_plan(const ConvGeom& g, unsigned al) {
+  CwPlan p{};
+  if (!cw_ok(g, al)) return p;
+  p.segw = g.Q <= 32 ? 32 : 64;
+  const int tr = (g.K == 256 ? 128 : 256) / p.segw;
+  p.tiles_h = (g.P + tr - 1) / tr;
+  p.tiles_w = (g.Q + p.segw - 1) / p.segw;
+  p.nt = (long long)g.N * p.tiles_h * p.tiles_w;
+  p.ok = p.nt < (1ll << 31);
+  return p;
 }
 
 typedef void (*CwKernel)(ConvGeom, const uint16_t*, const uint16_t*, const float*, uint16_t*, double*, int, int, int,
@@ -3890,11 +3936,10 @@ static CwKernel cw_kernel(int segw, bool drop) {
 template <bool RES>
 static int launch_cw(const ConvGeom& g, const void* x, const void* wp, const float* bias, void* y, double* stats,
                      int srows, hipStream_t s, const char* what) {
-  if (!cw_ok(g, x, wp, y) || (RES && g.drop.on)) return ACFE_E_INVAL;
-  const int segw = g.Q <= 32 ? 32 : 64, tr = (g.K == 256 ? 128 : 256) / segw;
-  const int tiles_h = (g.P + tr - 1) / tr, tiles_w = (g.Q + segw - 1) / segw;
-  const long long nt = (long long)g.N * tiles_h * tiles_w;
-  if (nt >= (1ll << 31)) return ACFE_E_INVAL;
+  const CwPlan cp = cw_plan(g, fwd_align(x, wp, y));
+  if (!cp.ok || (RES && g.drop.on)) return ACFE_E_INVAL;
+  const int segw = cp.segw, tiles_h = cp.tiles_h, tiles_w = cp.tiles_w;
+  const long long nt = cp.nt;
   const CwKernel k = g.C == 32 ? cw_kernel<32, 128, RES>(segw, g.drop.on) : cw_kernel<16, 256, RES>(segw, g.drop.on);
   hipLaunchKernelGGL(k, dim3(tile_grid(nt, stats != nullptr, srows)), dim3(512), 0, s, g, (const uint16_t*)x,
                      (const uint16_t*)wp, bias, (uint16_t*)y, stats, tiles_h, tiles_w, (int)nt, srows);
@@ -3915,47 +3960,136 @@ static void launch_narrow(const ConvGeom& g, const void* x, const void* wp, cons
                        tiles_h, tiles_w, (int)nt, grid_m);
 }
 
-template <typename T, int BN, int WM, int WN>
-static int launch_fwd_t(const ConvGeom& g, const void* x, const void* wp, const float* bias, void* y,
-                        double* stats, int grid_m, hipStream_t s) {
-  const int tiles_m = (int)((g.M + 127) / 128);
-  dim3 grid(grid_m, g.Kp / BN);
-  if constexpr (sizeof(T) == 2 && BN >= 64) {
-    if (g.R == 3 && g.S == 3 && g.st == 1 && g.C % 64 == 0 && g.K == BN && (!g.drop.on || g.idx32) &&
-        ((uintptr_t)y & 15) == 0) {  // (16-B epilogue stores)
+// The forward dispatch's answer: the leaf (ACFE_FWD_*), its template choice
+// (a, b) -- (NCS, NKB) of k_conv1x1_reg, (KB, SEGW) of k_conv3x3_cw / _narrow,
+// (BN, 0) otherwise --, the launch grid and the tile count the grid walks
+// (ACFE_FWD_ROWS: the grids are launch_plain1w's / launch_r64's / the row
+// kernel's own, 0 here), and the tile split of the 3x3 leaves.
+struct FwdPick {
+  int leaf, a, b, gx, gy, tiles;
+  int tiles_h, tiles_w;
+};
+
+// bf16: the element type; al: FWD_AL_* of x / wpacked / y; drop: a fused
+// Dropout; stats: a statistics slab (of grid_m rows) is written; grid_m:
+// grid_m_for(M, Kp / pick_bn(K)), the generic kernels' grid rows = slab rows
+static FwdPick fwd_pick(const ConvGeom& g, bool bf16, unsigned al, bool drop, bool stats, int grid_m) {
+  FwdPick f{};
+  const bool same3 = g.R == 3 && g.S == 3 && g.st == 1 && g.pt == 1 && g.pl == 1 && g.P == g.H && g.Q == g.W;
+  // (k_conv1x1_reg maps output pixel m to input pixel m: P x Q must be H x W --
+  // the strided dgrad's phase convs can have one more output row / column)
+  if (bf16 && g.R == 1 && g.S == 1 && g.st == 1 && g.pt == 0 && g.pl == 0 && g.P == g.H && g.Q == g.W &&
+      g.C % 8 == 0 && g.K % 4 == 0 && g.ldy == g.K && ((g.C <= 32 && g.K <= 128) || (g.K <= 32 && g.C <= 128))) {
+    const int ncs = (g.C + 31) / 32, nkb = (g.K + 15) / 16;
+    // (WIDE tile stores whole 16-channel blocks); the instantiated (reduction
+    // steps, 16-channel output blocks)
+    const bool wide_ok = nkb < 4 || g.K == nkb * 16;
+    const bool inst = (ncs == 1 && (nkb == 1 || nkb == 2 || nkb == 4 || nkb == 8)) ||
+                      (ncs == 2 && (nkb == 1 || nkb == 2)) || (ncs == 4 && (nkb == 1 || nkb == 2));
+    if (wide_ok && inst) {
+      f.leaf = ACFE_FWD_1X1_REG;
+      f.a = ncs;
+      f.b = nkb;
+      f.gx = grid_m;
+      f.gy = 1;
+      f.tiles = (int)std::min<long long>((g.M + 15) / 16, 0x7fffffff);  // 16-pixel blocks
+      return f;
+    }
+  }
+  if (bf16) {
+    if (same3 && g.C == 16 && g.K == 64 && g.Kp == 64 && g.Kdp >= 160 && g.ldy == g.K && g.M * g.K < (1ll << 32) &&
+        (al & FWD_AL_X16) && (al & FWD_AL_W16) && (al & FWD_AL_Y8)) {
+      const int tiles_h = (g.P + 7) / 8, tiles_w = (g.Q + 63) / 64;
+      const long long nt = (long long)g.N * tiles_h * tiles_w;
+      if (nt < (1ll << 31)) {
+        f = {ACFE_FWD_C16, 0, 0, tile_grid(nt, stats, grid_m), 1, (int)nt, tiles_h, tiles_w};
+        return f;
+      }
+    }
+    if (const CwPlan cp = cw_plan(g, al); cp.ok) {
+      f = {ACFE_FWD_CW, g.K, cp.segw, tile_grid(cp.nt, stats, grid_m), 1, (int)cp.nt, cp.tiles_h, cp.tiles_w};
+      return f;
+    }
+    if (same3 && g.C % 64 == 0 && (g.K == 32 || g.K == 16) && g.C * g.K <= 4096 && g.ldy == g.K &&
+        g.M * g.K < (1ll << 32)) {
+      constexpr int nw = 8;
+      // tiles of nw * 32 pixels: segw columns x tr rows
+      const int segw = g.Q <= 32 ? 32 : 64, tr = nw * 32 / segw;
+      const int tiles_h = (g.P + tr - 1) / tr, tiles_w = (g.Q + segw - 1) / segw;
+      const long long nt = (long long)g.N * tiles_h * tiles_w;
+      if (nt < (1ll << 31)) {
+        f = {ACFE_FWD_NARROW, g.K, segw, tile_grid(nt, stats, grid_m), 1, (int)nt, tiles_h, tiles_w};
+        return f;
+      }
+    }
+  }
+  const int bn = pick_bn(g.K);
+  if (bf16 && bn >= 64) {
+    if (g.R == 3 && g.S == 3 && g.st == 1 && g.C % 64 == 0 && g.K == bn && (!drop || g.idx32) &&
+        (al & FWD_AL_Y16)) {  // (16-B epilogue stores)
       // chunk-resident halo rows: 4-row tiles at K = 128, 8 at K = 64 (r02z-ba:
       // the 6-row per-step staging, 3-row and 5-row tiles all measured slower)
-      constexpr int tr = BN == 128 ? 4 : 8;
+      const int tr = bn == 128 ? 4 : 8;
       const int tiles_h = (g.P + tr - 1) / tr, tiles_w = (g.Q + 63) / 64;  // partial last column tile
       const long long nt = (long long)g.N * tiles_h * tiles_w;
       if (nt < (1ll << 31)) {
-        const int gp = tile_grid(nt, stats != nullptr, grid_m);
-        if constexpr (BN == 128) {
-          // one wave per SIMD (pool1w.hip), the previous tile's epilogue beside this tile's MFMAs
-          const int rc = launch_plain1w(g, x, wp, bias, y, stats, grid_m, s, "acfe_conv2d_fwd", 0);
-          if (rc != ACFE_E_INVAL) return rc;
-        }
-        if constexpr (BN == 64) {
-          // the epilogue beside the next tile's MFMAs (rows64.hip)
-          const int rc = launch_r64(g, x, wp, bias, y, stats, grid_m, s, "acfe_conv2d_fwd", g.drop.on ? 4 : 0);
-          if (rc != ACFE_E_INVAL) return rc;
-        }
+        f = {ACFE_FWD_ROWS, bn, 0, 0, 0, 0, tiles_h, tiles_w};
+        return f;
+      }
+    }
+    if (fwd_p_ok(g, bn)) {
+      f.leaf = ACFE_FWD_P;
+      f.a = bn;
+      fwd_p_grid(g, bn, &f.gx, &f.gy, &f.tiles);
+      return f;
+    }
+  }
+  f.leaf = g.C % (bf16 ? TT<uint16_t>::GR : TT<float>::GR) == 0 ? ACFE_FWD_G : ACFE_FWD_GENERIC;
+  f.a = bn;
+  f.gx = grid_m;
+  f.gy = g.Kp / bn;
+  f.tiles = (int)((g.M + 127) / 128);
+  return f;
+}
+
+// ACFE_FWD_ROWS at BN output channels: launch_plain1w (K = 128) / launch_r64
+// (K = 64) where they take the shape, else k_conv3x3_rows
+template <int BN>
+static int launch_fwd_rows(const ConvGeom& g, const FwdPick& f, const void* x, const void* wp, const float* bias,
+                           void* y, double* stats, int grid_m, hipStream_t s) {
+  constexpr int tr = BN == 128 ? 4 : 8;
+  const int tiles_h = f.tiles_h, tiles_w = f.tiles_w;
+  const long long nt = (long long)g.N * tiles_h * tiles_w;
+  const int gp = tile_grid(nt, stats != nullptr, grid_m);
+  if constexpr (BN == 128) {
+    // one wave per SIMD (pool1w.hip), the previous tile's epilogue beside this tile's MFMAs
+    const int rc = launch_plain1w(g, x, wp, bias, y, stats, grid_m, s, "acfe_conv2d_fwd", 0);
+    if (rc != ACFE_E_INVAL) return rc;
+  }
+  if constexpr (BN == 64) {
+    // the epilogue beside the next tile's MFMAs (rows64.hip)
+    const int rc = launch_r64(g, x, wp, bias, y, stats, grid_m, s, "acfe_conv2d_fwd", g.drop.on ? 4 : 0);
+    if (rc != ACFE_E_INVAL) return rc;
+  }
 #define ROWS(TR_, PM_, ...)                                                                                   \
   hipLaunchKernelGGL((k_conv3x3_rows<BN, TR_, PM_, ##__VA_ARGS__>), dim3(gp), dim3(512), 0, s, g, (const uint16_t*)x, \
                      (const uint16_t*)wp, bias, (uint16_t*)y, stats, tiles_h, tiles_w, (int)nt, grid_m, nullptr)
-        if (g.drop.on) ROWS(tr, 4, true); else ROWS(tr, 0, true);
+  if (g.drop.on) ROWS(tr, 4, true); else ROWS(tr, 0, true);
 #undef ROWS
-        return launch_rc("acfe_conv2d_fwd");
-      }
-    }
-    if (fwd_p_ok(g, BN)) return launch_fwd_p<BN, false>(g, x, wp, bias, y, stats, grid_m, s, "acfe_conv2d_fwd");
-  }
-  if (g.C % TT<T>::GR == 0)
+  return launch_rc("acfe_conv2d_fwd");
+}
+
+// ACFE_FWD_G / ACFE_FWD_GENERIC at BN output channels per tile
+template <typename T, int BN, int WM, int WN>
+static int launch_fwd_t(const ConvGeom& g, const FwdPick& f, const void* x, const void* wp, const float* bias,
+                        void* y, double* stats, hipStream_t s) {
+  const dim3 grid(f.gx, f.gy);
+  if (f.leaf == ACFE_FWD_G)
     hipLaunchKernelGGL((k_conv_fwd_g<T, 128, BN, WM, WN>), grid, dim3(256), 0, s, g, (const T*)x,
-                       (const T*)wp, bias, (T*)y, stats, tiles_m);
+                       (const T*)wp, bias, (T*)y, stats, f.tiles);
   else
     hipLaunchKernelGGL((k_conv_fwd<T, 128, BN, WM, WN, false>), grid, dim3(256), 0, s, g, (const T*)x,
-                       (const T*)wp, bias, (T*)y, stats, tiles_m);
+                       (const T*)wp, bias, (T*)y, stats, f.tiles);
   return launch_rc("acfe_conv2d_fwd");
 }
 
@@ -3970,66 +4104,51 @@ static int launch_1x1(const ConvGeom& g, const void* x, const void* wp, const fl
 template <typename T>
 static int launch_fwd(const ConvGeom& g, const void* x, const void* wp, const float* bias, void* y,
                       double* stats, int grid_m, hipStream_t s) {
-  // (k_conv1x1_reg maps output pixel m to input pixel m: P x Q must be H x W --
-  // the strided dgrad's phase convs can have one more output row / column)
-  if (sizeof(T) == 2 && g.R == 1 && g.S == 1 && g.st == 1 && g.pt == 0 && g.pl == 0 && g.P == g.H &&
-      g.Q == g.W && g.C % 8 == 0 && g.K % 4 == 0 && g.ldy == g.K &&
-      ((g.C <= 32 && g.K <= 128) || (g.K <= 32 && g.C <= 128))) {
-    const int ncs = (g.C + 31) / 32, nkb = (g.K + 15) / 16;
-    if (nkb >= 4 && g.K != nkb * 16) goto general;  // WIDE tile stores whole 16-channel blocks
-    // dispatch on (reduction steps, 16-channel output blocks)
-#define L1(A, B) if (ncs == A && nkb == B) return launch_1x1<A, B>(g, x, wp, bias, y, stats, grid_m, s)
-    L1(1, 1); L1(1, 2); L1(1, 4); L1(1, 8);
-    L1(2, 1); L1(2, 2); L1(4, 1); L1(4, 2);
+  constexpr bool bf16 = sizeof(T) == 2;
+  const FwdPick f = fwd_pick(g, bf16, fwd_align(x, wp, y), g.drop.on != 0, stats != nullptr, grid_m);
+  if constexpr (bf16) {
+    const uint16_t *xx = (const uint16_t*)x, *ww = (const uint16_t*)wp;
+    uint16_t* yy = (uint16_t*)y;
+    const int th = f.tiles_h, tw = f.tiles_w;
+    switch (f.leaf) {
+      case ACFE_FWD_1X1_REG:
+#define L1(A, B) if (f.a == A && f.b == B) return launch_1x1<A, B>(g, x, wp, bias, y, stats, grid_m, s)
+        L1(1, 1); L1(1, 2); L1(1, 4); L1(1, 8);
+        L1(2, 1); L1(2, 2); L1(4, 1); L1(4, 2);
 #undef L1
-  }
-general:
-  if constexpr (sizeof(T) == 2) {
-    if (g.R == 3 && g.S == 3 && g.st == 1 && g.pt == 1 && g.pl == 1 && g.P == g.H && g.Q == g.W && g.C == 16 &&
-        g.K == 64 && g.Kp == 64 && g.Kdp >= 160 && g.ldy == g.K && g.M * g.K < (1ll << 32) &&
-        ((uintptr_t)x & 15) == 0 && ((uintptr_t)wp & 15) == 0 && ((uintptr_t)y & 7) == 0) {
-      const int tiles_h = (g.P + 7) / 8, tiles_w = (g.Q + 63) / 64;
-      const long long nt = (long long)g.N * tiles_h * tiles_w;
-      if (nt < (1ll << 31)) {
-        const int gp = tile_grid(nt, stats != nullptr, grid_m);
+        return ACFE_E_INVAL;  // (not reached: fwd_pick names instantiated pairs only)
+      case ACFE_FWD_C16:
         if (g.drop.on)
-          hipLaunchKernelGGL(k_conv3x3_c16<true>, dim3(gp), dim3(512), 0, s, g, (const uint16_t*)x,
-                             (const uint16_t*)wp, bias, (uint16_t*)y, stats, tiles_h, tiles_w, (int)nt, grid_m);
+          hipLaunchKernelGGL(k_conv3x3_c16<true>, dim3(f.gx), dim3(512), 0, s, g, xx, ww, bias, yy, stats, f.tiles_h,
+                             f.tiles_w, f.tiles, grid_m);
         else
-          hipLaunchKernelGGL(k_conv3x3_c16<false>, dim3(gp), dim3(512), 0, s, g, (const uint16_t*)x,
-                             (const uint16_t*)wp, bias, (uint16_t*)y, stats, tiles_h, tiles_w, (int)nt, grid_m);
+          hipLaunchKernelGGL(k_conv3x3_c16<false>, dim3(f.gx), dim3(512), 0, s, g, xx, ww, bias, yy, stats, f.tiles_h,
+                             f.tiles_w, f.tiles, grid_m);
         return launch_rc("acfe_conv2d_fwd(c16)");
-      }
-    }
-    {
-      const int rc = launch_cw<false>(g, x, wp, bias, y, stats, grid_m, s, "acfe_conv2d_fwd(cw)");
-      if (rc != ACFE_E_INVAL) return rc;
-    }
-    if (g.R == 3 && g.S == 3 && g.st == 1 && g.pt == 1 && g.pl == 1 && g.P == g.H && g.Q == g.W &&
-        g.C % 64 == 0 && (g.K == 32 || g.K == 16) && g.C * g.K <= 4096 && g.ldy == g.K &&
-        g.M * g.K < (1ll << 32)) {
-      constexpr int nw = 8;
-      // tiles of nw * 32 pixels: segw columns x tr rows
-      const int segw = g.Q <= 32 ? 32 : 64, tr = nw * 32 / segw;
-      const int tiles_h = (g.P + tr - 1) / tr, tiles_w = (g.Q + segw - 1) / segw;
-      const long long nt = (long long)g.N * tiles_h * tiles_w;
-      if (nt < (1ll << 31)) {
-        const int gp = tile_grid(nt, stats != nullptr, grid_m);
+      case ACFE_FWD_CW:
+        return launch_cw<false>(g, x, wp, bias, y, stats, grid_m, s, "acfe_conv2d_fwd(cw)");
+      case ACFE_FWD_NARROW:
         if (g.K == 32) {
-          if (segw == 64) launch_narrow<32, 64>(g, x, wp, bias, y, stats, tiles_h, tiles_w, nt, grid_m, gp, s);
-          else launch_narrow<32, 32>(g, x, wp, bias, y, stats, tiles_h, tiles_w, nt, grid_m, gp, s);
+          if (f.b == 64) launch_narrow<32, 64>(g, x, wp, bias, y, stats, th, tw, f.tiles, grid_m, f.gx, s);
+          else launch_narrow<32, 32>(g, x, wp, bias, y, stats, th, tw, f.tiles, grid_m, f.gx, s);
         } else {
-          if (segw == 64) launch_narrow<16, 64>(g, x, wp, bias, y, stats, tiles_h, tiles_w, nt, grid_m, gp, s);
-          else launch_narrow<16, 32>(g, x, wp, bias, y, stats, tiles_h, tiles_w, nt, grid_m, gp, s);
+          if (f.b == 64) launch_narrow<16, 64>(g, x, wp, bias, y, stats, th, tw, f.tiles, grid_m, f.gx, s);
+          else launch_narrow<16, 32>(g, x, wp, bias, y, stats, th, tw, f.tiles, grid_m, f.gx, s);
         }
         return launch_rc("acfe_conv2d_fwd(narrow)");
-      }
+      case ACFE_FWD_ROWS:
+        if (f.a == 64) return launch_fwd_rows<64>(g, f, x, wp, bias, y, stats, grid_m, s);
+        return launch_fwd_rows<128>(g, f, x, wp, bias, y, stats, grid_m, s);
+      case ACFE_FWD_P:
+        if (f.a == 64) return launch_fwd_p<64, false>(g, x, wp, bias, y, stats, grid_m, s, "acfe_conv2d_fwd");
+        return launch_fwd_p<128, false>(g, x, wp, bias, y, stats, grid_m, s, "acfe_conv2d_fwd");
+      default:
+        break;
     }
   }
-  const int bn = pick_bn(g.K);
-  if (bn == 32) return launch_fwd_t<T, 32, 4, 1>(g, x, wp, bias, y, stats, grid_m, s);
-  if (bn == 64) return launch_fwd_t<T, 64, 2, 2>(g, x, wp, bias, y, stats, grid_m, s);
-  return launch_fwd_t<T, 128, 2, 2>(g, x, wp, bias, y, stats, grid_m, s);
+  if (f.a == 32) return launch_fwd_t<T, 32, 4, 1>(g, f, x, wp, bias, y, stats, s);
+  if (f.a == 64) return launch_fwd_t<T, 64, 2, 2>(g, f, x, wp, bias, y, stats, s);
+  return launch_fwd_t<T, 128, 2, 2>(g, f, x, wp, bias, y, stats, s);
 }
 
 static int grid_m_for(long long M, int ny) {
@@ -4122,6 +4241,29 @@ ACFE_API int acfe_conv2d_fwd_dropout(const void* x, int N, int H, int W, int C, 
   if (drop_rate < 0.f || drop_rate >= 1.f) return ACFE_E_INVAL;
   return conv2d_fwd_impl(x, N, H, W, C, wpacked, K, R, S, stride, pad_top, pad_left, P, Q, bias, y, dtype,
                          stats_partial, make_drop(drop_rate, seed), stream);
+}
+
+// Which kernel acfe_conv2d_fwd / acfe_conv2d_fwd_dropout (dropout != 0) runs for
+// the geometry (host only, no GPU call): fwd_pick's answer for 16-byte-aligned
+// x, wpacked and y as out = {leaf (ACFE_FWD_*), a, b, grid_x, grid_y, tiles};
+// stats: a statistics slab is passed.  The stride-1 acfe_conv2d_dgrad is the
+// query of its forward call (dY's P x Q x K in, flipped pads, H x W x C out).
+// 1, or 0 with out zeroed on invalid arguments.
+ACFE_API int acfe_conv2d_fwd_info(int N, int H, int W, int C, int K, int R, int S, int stride, int pad_top,
+                                  int pad_left, int P, int Q, int dtype, int dropout, int stats, int* out) {
+  if (!out) return 0;
+  for (int i = 0; i < 6; ++i) out[i] = 0;
+  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || R <= 0 || S <= 0 || stride <= 0 || P <= 0 || Q <= 0 ||
+      (dtype != 0 && dtype != 1))
+    return 0;
+  const int BK = dtype == ACFE_DTYPE_BF16 ? 64 : 32;
+  const int bn = pick_bn(K);
+  const ConvGeom g = make_geom(N, H, W, C, K, R, S, stride, pad_top, pad_left, P, Q, BK, bn);
+  const FwdPick f = fwd_pick(g, dtype == ACFE_DTYPE_BF16, FWD_AL_ALL, dropout != 0, stats != 0,
+                             grid_m_for(g.M, g.Kp / bn));
+  const int v[6] = {f.leaf, f.a, f.b, f.gx, f.gy, f.tiles};
+  for (int i = 0; i < 6; ++i) out[i] = v[i];
+  return 1;
 }
 
 // dX = conv^T(dY, W).  wflip = acfe_conv2d_pack_weights(..., flip=1).
@@ -4402,10 +4544,13 @@ ACFE_API int acfe_conv2d_dgrad(const void* dy, int N, int P, int Q, int K, const
 
 // Split-K plan of the wgrad: `splits` pixel chunks of `chunk` rows, splits a
 // multiple of 8 so the XCD mapping of k_conv_wgrad is a bijection.
+// k_wgrad_reduce_g (split-parallel, 16-B vectors) from 16 splits on; else k_wgrad_reduce
+static bool wgrad_reduce_g_ok(long long nsplit, long long n, bool aligned16) {
+  return (n & 3) == 0 && aligned16 && nsplit >= 16;
+}
 static void wgrad_combine(const float* ws, int nsplit, long long n, float beta, float* dw, int grid,
                           hipStream_t st) {
-  const bool vec = (n & 3) == 0 && ((uintptr_t)ws & 15) == 0 && ((uintptr_t)dw & 15) == 0;
-  if (vec && nsplit >= 16) {
+  if (wgrad_reduce_g_ok(nsplit, n, ((uintptr_t)ws & 15) == 0 && ((uintptr_t)dw & 15) == 0)) {
     const long long nv = n >> 2;
     hipLaunchKernelGGL(k_wgrad_reduce_g, dim3((unsigned)((nv + 15) / 16)), dim3(256), 0, st, ws, nsplit, nv, n, beta,
                        dw);
@@ -4448,12 +4593,23 @@ static int wgrad_finish(const float* ws, int used, int K, int kd, float beta, fl
   return launch_rc(what);
 }
 
+// Which kernel acfe_conv2d_wgrad runs (path: 0 k_conv_wgrad, 1 k_wgrad3x3_halo,
+// 2 k_wgrad_row_halo) and, for path 0, its instantiation <BMW, FAST_D, FAST_X>,
+// split-K plan and (kd, K) tile count; the launcher switches on it and the
+// host-only query acfe_conv2d_wgrad_info returns it
+struct WgradPick {
+  int path, bmw;
+  bool fd, fx;
+  long long splits, chunk;
+  int tiles;
+};
 template <typename T, int BMW>
-static int launch_wgrad_t(const ConvGeom& g, const void* x, const void* dy, float* ws, long long chunk,
-                          int splits, hipStream_t s) {
+static int launch_wgrad_t(const ConvGeom& g, const void* x, const void* dy, float* ws, const WgradPick& w,
+                          hipStream_t s) {
   const int tx = (g.Kd + 127) / 128, ty = (g.K + BMW - 1) / BMW;
-  dim3 grid(tx * ty * splits);  // 1-D: k_conv_wgrad maps it XCD-aware
-  const bool fd = g.K % TT<T>::GR == 0, fx = g.C % TT<T>::GR == 0;
+  const long long chunk = w.chunk;
+  const bool fd = w.fd, fx = w.fx;
+  dim3 grid(tx * ty * (int)w.splits);  // 1-D: k_conv_wgrad maps it XCD-aware
 #define WG(FD, FX)                                                                                       \
   hipLaunchKernelGGL((k_conv_wgrad<T, BMW, FD, FX>), grid, dim3(256), 0, s, g, (const T*)x, (const T*)dy, \
                      ws, chunk, tx, ty)
@@ -4629,43 +4785,90 @@ static bool halo_ok(int N, int C, int K, int R, int S, int stride, int P, int Q,
          (long long)N * P * ((Q + 63) / 64) < (1ll << 31);
 }
 
+static WgradPick wgrad_pick(int N, int C, int K, int R, int S, int stride, int P, int Q, int dtype) {
+  const long long M = (long long)N * P * Q;
+  const int kd = R * S * C;
+  const bool bf16 = dtype == ACFE_DTYPE_BF16;
+  WgradPick w{};
+  const WgradPlan pl = wgrad_plan(M, kd, K);
+  w.splits = pl.splits;
+  w.chunk = pl.chunk;
+  w.bmw = K <= 32 ? 32 : (K <= 64 ? 64 : 128);
+  if (bf16 && halo_ok(N, C, K, R, S, stride, P, Q, pl.splits)) {
+    w.path = 1;
+  } else if (bf16 && S == 10 && stride == 1 && C % 64 == 0 && K == 128 &&
+             (long long)N * P * ((Q + 31) / 32) < (1ll << 31)) {
+    w.path = 2;
+  } else {
+    const int gr = bf16 ? TT<uint16_t>::GR : TT<float>::GR;
+    w.path = 0;
+    w.fd = K % gr == 0;
+    w.fx = C % gr == 0;
+    w.tiles = ((kd + 127) / 128) * ((K + w.bmw - 1) / w.bmw);
+  }
+  return w;
+}
+
 // dW[k][r][s][c] (fp32, KRSC) = sum over pixels.  beta: dW = beta*dW + grad.
 ACFE_API int acfe_conv2d_wgrad(const void* x, int N, int H, int W, int C, const void* dy, int K, int R, int S,
                                int stride, int pad_top, int pad_left, int P, int Q, float* dw, float beta,
                                int dtype, float* workspace, void* stream) {
   if (!x || !dy || !dw || !workspace || N < 0 || C <= 0 || K <= 0 || (dtype != 0 && dtype != 1))
     return ACFE_E_INVAL;
-  const long long M = (long long)N * P * Q;
   const int kd = R * S * C;
   if (N == 0) return hip_rc(hipMemsetAsync(dw, 0, sizeof(float) * K * kd, strm(stream)), "wgrad");
-  const int bmw = K <= 32 ? 32 : (K <= 64 ? 64 : 128);
-  auto [splits, chunk] = wgrad_plan(M, kd, K);
+  const WgradPick w = wgrad_pick(N, C, K, R, S, stride, P, Q, dtype);
+  long long splits = w.splits;
   ConvGeom g = make_geom(N, H, W, C, K, R, S, stride, pad_top, pad_left, P, Q, 64, 128);
   int rc;
-  if (dtype == ACFE_DTYPE_BF16 && halo_ok(N, C, K, R, S, stride, P, Q, splits)) {
+  if (w.path == 1) {
     // halo-staged kernel; its split count stays within the planned workspace
     int used = 0;
     rc = wgrad_halo_launch(g, x, dy, nullptr, workspace, splits, strm(stream), &used);
     if (rc) return rc;
     splits = used;
-  } else if (dtype == ACFE_DTYPE_BF16 && S == 10 && stride == 1 && C % 64 == 0 && K == 128 &&
-             (long long)N * P * ((Q + 31) / 32) < (1ll << 31)) {
+  } else if (w.path == 2) {
     int used = 0;
     rc = wgrad_row_halo_launch(g, x, dy, workspace, splits, strm(stream), &used);
     if (rc) return rc;
     splits = used;
   } else if (dtype == ACFE_DTYPE_BF16) {
-    if (bmw == 32) rc = launch_wgrad_t<uint16_t, 32>(g, x, dy, workspace, chunk, (int)splits, strm(stream));
-    else if (bmw == 64) rc = launch_wgrad_t<uint16_t, 64>(g, x, dy, workspace, chunk, (int)splits, strm(stream));
-    else rc = launch_wgrad_t<uint16_t, 128>(g, x, dy, workspace, chunk, (int)splits, strm(stream));
+    if (w.bmw == 32) rc = launch_wgrad_t<uint16_t, 32>(g, x, dy, workspace, w, strm(stream));
+    else if (w.bmw == 64) rc = launch_wgrad_t<uint16_t, 64>(g, x, dy, workspace, w, strm(stream));
+    else rc = launch_wgrad_t<uint16_t, 128>(g, x, dy, workspace, w, strm(stream));
     if (rc) return rc;
   } else {
-    if (bmw == 32) rc = launch_wgrad_t<float, 32>(g, x, dy, workspace, chunk, (int)splits, strm(stream));
-    else if (bmw == 64) rc = launch_wgrad_t<float, 64>(g, x, dy, workspace, chunk, (int)splits, strm(stream));
-    else rc = launch_wgrad_t<float, 128>(g, x, dy, workspace, chunk, (int)splits, strm(stream));
+    if (w.bmw == 32) rc = launch_wgrad_t<float, 32>(g, x, dy, workspace, w, strm(stream));
+    else if (w.bmw == 64) rc = launch_wgrad_t<float, 64>(g, x, dy, workspace, w, strm(stream));
+    else rc = launch_wgrad_t<float, 128>(g, x, dy, workspace, w, strm(stream));
     if (rc) return rc;
   }
   return wgrad_finish(workspace, (int)splits, K, kd, beta, dw, strm(stream), "acfe_conv2d_wgrad(reduce)");
+}
+
+// The weight-gradient launch of the shape (host only, no GPU call): wgrad_pick's
+// answer as out = {path, bmw, fast_d, fast_x, splits, chunk, tiles, reduce};
+// reduce: 1 where the split slabs are summed by k_wgrad_reduce_g (16-byte-
+// aligned workspace and dw assumed).  Paths 1 and 2 fill `path` only (the halo
+// plan: acfe_conv2d_wgrad_halo_info).  1, or 0 with out zeroed on invalid arguments.
+ACFE_API int acfe_conv2d_wgrad_info(int N, int H, int W, int C, int K, int R, int S, int stride, int P, int Q,
+                                    int dtype, int* out) {
+  if (!out) return 0;
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || R <= 0 || S <= 0 || stride <= 0 || P <= 0 || Q <= 0 ||
+      (dtype != 0 && dtype != 1))
+    return 0;
+  const WgradPick w = wgrad_pick(N, C, K, R, S, stride, P, Q, dtype);
+  out[0] = w.path;
+  if (w.path != 0) return 1;
+  if (w.chunk >= (1ll << 31) || w.splits >= (1ll << 31)) {
+    out[0] = 0;
+    return 0;
+  }
+  const int v[8] = {0, w.bmw, w.fd ? 1 : 0, w.fx ? 1 : 0, (int)w.splits, (int)w.chunk, w.tiles,
+                    wgrad_reduce_g_ok(w.splits, (long long)K * R * S * C, true) ? 1 : 0};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
+  return 1;
 }
 
 // ------------------------------------------------------------------ wgrad + BN backward apply

@@ -230,6 +230,37 @@ int acfe_conv2d_fwd_dropout(const void* x, int N, int H, int W, int C, const voi
                             int stride, int pad_top, int pad_left, int P, int Q, const float* bias, void* y,
                             int dtype, double* stats_partial, float drop_rate, unsigned long long seed,
                             void* stream);
+/* Which kernel acfe_conv2d_fwd (dropout = 0) / acfe_conv2d_fwd_dropout
+ * (dropout = 1) launches for the geometry: host only, no GPU call, decided by
+ * the launcher's own dispatch function.  stats: 1 when a statistics slab is
+ * passed (it caps some grids at the slab's rows).  The query ASSUMES x, wpacked
+ * and y 16-byte aligned (a less aligned pointer moves some shapes onto a more
+ * general kernel).  out[6] = {leaf, a, b, grid_x, grid_y, tiles}:
+ *   ACFE_FWD_1X1_REG  k_conv1x1_reg<a = NCS, b = NKB>; tiles: 16-pixel blocks
+ *   ACFE_FWD_C16      k_conv3x3_c16 (16 -> 64); a = b = 0; tiles: 8 x 64 tiles
+ *   ACFE_FWD_CW       k_conv3x3_cw<a = KB, b = SEGW>
+ *   ACFE_FWD_NARROW   k_conv3x3_narrow<a = KB, b = SEGW>
+ *   ACFE_FWD_ROWS     the 3x3 row-tile family at a = BN output channels
+ *                     (k_conv3x3_1w / k_conv3x3_r64 where they take the shape,
+ *                     else k_conv3x3_rows: decided in their own launchers, not
+ *                     distinguished here); b = 0, grid and tiles 0
+ *   ACFE_FWD_P        k_conv_fwd_p<a = BN>; tiles: 256-pixel M tiles
+ *   ACFE_FWD_G        k_conv_fwd_g<T, 128, a = BN>; tiles: 128-pixel M tiles
+ *   ACFE_FWD_GENERIC  k_conv_fwd<T, 128, a = BN> (C not a multiple of the load
+ *                     granule: 8 bf16 / 4 fp32)
+ * The stride-1 acfe_conv2d_dgrad(dy[N,P,Q,K] -> dx[N,H,W,C]) is the query of
+ * (N, P, Q, K, C, R, S, 1, R-1-pad_top, S-1-pad_left, H, W).  Returns 1, or 0
+ * with out zeroed on invalid arguments. */
+#define ACFE_FWD_1X1_REG 1
+#define ACFE_FWD_C16 2
+#define ACFE_FWD_CW 3
+#define ACFE_FWD_NARROW 4
+#define ACFE_FWD_ROWS 5
+#define ACFE_FWD_P 6
+#define ACFE_FWD_G 7
+#define ACFE_FWD_GENERIC 8
+int acfe_conv2d_fwd_info(int N, int H, int W, int C, int K, int R, int S, int stride, int pad_top, int pad_left,
+                         int P, int Q, int dtype, int dropout, int stats, int* out);
 /* dX of the convolution above (wflip = flip=1 packing).  stride > 1 runs the
  * st x st sub-pixel phases as stride-1 convs of dY with the phase sub-kernels
  * (no zero insertion) and needs `workspace` of acfe_conv2d_dgrad_workspace
@@ -268,6 +299,17 @@ long long acfe_conv2d_wgrad_workspace(int N, int H, int W, int C, int K, int R, 
 int acfe_conv2d_wgrad(const void* x, int N, int H, int W, int C, const void* dy, int K, int R, int S,
                       int stride, int pad_top, int pad_left, int P, int Q, float* dw, float beta, int dtype,
                       float* workspace, void* stream);
+/* Which kernel acfe_conv2d_wgrad launches for the shape: host only, no GPU
+ * call, decided by the launcher's own plan functions.  out[8] = {path, bmw,
+ * fast_d, fast_x, splits, chunk, tiles, reduce}: path 0 the generic split-K
+ * k_conv_wgrad<T, bmw, fast_d, fast_x> over `splits` pixel ranges of `chunk`
+ * pixels and `tiles` (R*S*C, K) tiles each, path 1 the halo kernel (its plan:
+ * acfe_conv2d_wgrad_halo_info), path 2 the (4, 10) head conv's row-halo
+ * kernel; reduce = 1 where the split slabs are summed by the split-parallel
+ * reduction (16-byte-aligned workspace and dw assumed).  Paths 1 and 2 fill
+ * `path` only.  Returns 1, or 0 with out zeroed on invalid arguments. */
+int acfe_conv2d_wgrad_info(int N, int H, int W, int C, int K, int R, int S, int stride, int P, int Q, int dtype,
+                           int* out);
 /* The wgrad of a bf16 3x3 stride-1 "same" conv whose output feeds [Dropout ->]
  * BatchNormalization (+ReLU) -- resnet/wr_resnet.py:58-71 (conv2a -> Dropout ->
  * bn2b -> ReLU), resnet/wr_resnet_bird.py:139-154 (conv21 -> Dropout -> bn2b)

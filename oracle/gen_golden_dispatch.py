@@ -34,7 +34,7 @@ CHANNELS = list(itertools.product(CS, KS))
 
 SHAPE_QUERIES = ("halo_info", "halo_info_fold", "halo_info_unpool", "wgrad_bnbwd_rows", "wgrad_workspace",
                  "stats_rows", "dropout_keep_supported", "pool_supported", "rows_supported", "fwd_add_supported",
-                 "bn_prologue_supported", "dgrad_bn_rows")
+                 "bn_prologue_supported", "dgrad_bn_rows", "fwd_leaf")
 
 
 def dispatch_switches():
@@ -50,8 +50,15 @@ def _halo(lib, N, H, W, C, K, fold, unpool):
     return list(out) if lib.acfe_conv2d_wgrad_halo_info(N, H, W, C, K, fold, unpool, out) else 0
 
 
+def _fwd_leaf(lib, N, H, W, C, K):
+    """{leaf, a, b} of acfe_conv2d_fwd_info: no dropout, with a statistics slab."""
+    out = (ctypes.c_int * 6)()
+    return list(out)[:3] if lib.acfe_conv2d_fwd_info(N, H, W, C, K, 3, 3, 1, 1, 1, H, W, BF16, 0, 1, out) else 0
+
+
 def shape_answers(lib, N, H, W, C, K):
-    """One value per SHAPE_QUERIES entry (a halo plan is its 8 fields, or 0)."""
+    """One value per SHAPE_QUERIES entry (a halo plan is its 8 fields, the
+    forward leaf its first 3, or 0)."""
     return [
         _halo(lib, N, H, W, C, K, 0, 0),
         _halo(lib, N, H, W, C, K, 1, 0),
@@ -65,6 +72,7 @@ def shape_answers(lib, N, H, W, C, K):
         lib.acfe_conv2d_fwd_add_supported(N, H, W, C, K, BF16),
         lib.acfe_conv2d_bn_prologue_supported(N, H, W, C, K, BF16),
         lib.acfe_conv2d_dgrad_bn_rows(N, H, W, C, K, 3, 3, 1, BF16),
+        _fwd_leaf(lib, N, H, W, C, K),
     ]
 
 
