@@ -144,6 +144,9 @@ SIGNATURES: dict[str, list] = {
     "acfe_resample_poly": [P, I32, I64, P, I32, I32, I32, I64, P, I64, P],
     "acfe_pcen_segments_workspace": [I32, I64],
     "acfe_pcen_normalize_segments": [P, I32, I64, P, I32, P, I32, P, P, P],
+    "acfe_mag_rownorm": [P, I32, I32, I32, P, P, P, F32, P, I32, P],
+    "acfe_leaky_bn": [P, C.c_longlong, I32, F32, P, P, P, I32, P],
+    "acfe_softmax": [P, I32, I32, P, P],
 }
 _RESTYPES = {"acfe_last_error": C.c_char_p, "acfe_conv2d_wgrad_workspace": I64, "acfe_conv2d_dgrad_workspace": I64, "acfe_crc32c": C.c_uint32,
              "acfe_c1bn_workspace": I64, "acfe_stft_mag_workspace": I64, "acfe_morph_box_workspace": I64,

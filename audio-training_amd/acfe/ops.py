@@ -1664,6 +1664,19 @@ def sigmoid(z: torch.Tensor) -> torch.Tensor:
     return p
 
 
+# badwinner2's inference passes (csrc/bw2.hip); their launchers are acfe/bw2.py
+from .bw2 import leaky_bn, mag_rownorm, softmax  # noqa: E402,F401
+
+
+def max_pool_valid(x: torch.Tensor, kh: int, kw: int) -> torch.Tensor:
+    """MaxPool2D((kh, kw)), "valid" with floor, of NHWC x by acfe_maxpool2d alone
+    (no argmax bytes: the forward of an inference-only model)."""
+    N, H, W, C = x.shape
+    y = _empty((N, H // kh, W // kw, C), x.dtype, x.device)
+    call("acfe_maxpool2d", ptr(x.contiguous()), N, H, W, C, kh, kw, ptr(y), dtype_code(x.dtype), stream())
+    return y
+
+
 LOSS_MODES = {"bce": 0, "binary": 0, "cce": 1, "categorical": 1}
 
 

@@ -2,6 +2,7 @@
 """Training driver of the acfe path (reference audiomodel.py:117-567, CLI :2238-2414).
 
   python audiomodel.py RUN_NAME -d DATA_DIR [--model-name wr-resnet-bird|wr-resnet]
+         (badwinner2 is accepted as a name but inference only: see predict.py)
          [--epochs E] [--batch-size B] [--n_mels 128] [--multi-label false] [--lr 0.01]
   multi-GPU:  python -m torch.distributed.run --nproc-per-node 8 audiomodel.py ...
 
@@ -50,12 +51,20 @@ def str2bool(v):
 
 
 MODEL_NAMES = {"wr-resnet": "wr_resnet", "wr-resnet-bird": "wr_resnet_bird", "wr_resnet": "wr_resnet",
-               "wr_resnet_bird": "wr_resnet_bird"}
+               "wr_resnet_bird": "wr_resnet_bird", "badwinner2": "badwinner2"}
+# built for prediction only (predict.py): the training entry refuses them
+INFERENCE_ONLY = {"badwinner2"}
 
 
-def build_model(model_name, input_shape, classes, dtype, dropout=0.1):
-    """AudioModel.build_model for the wr-resnet branches (audiomodel.py:776-780)."""
+def build_model(model_name, input_shape, classes, dtype, dropout=0.1, multi_label=True, lme=False):
+    """AudioModel.build_model for the wr-resnet branches (audiomodel.py:776-780)
+    and badwinner2 (:741-749; eval mode only -- multi_label and lme are its
+    arguments, the WRNs ignore them)."""
     kind = MODEL_NAMES[model_name]
+    if kind == "badwinner2":
+        import badwinner2
+
+        return badwinner2.build_model(input_shape, None, classes, multi_label=multi_label, lme=lme, dtype=dtype)
     if kind == "wr_resnet_bird":
         from resnet.wr_resnet_bird import WRResNet
     else:
@@ -173,6 +182,10 @@ def shard_files(files, rank, world):
 
 
 def train_model(args):
+    if MODEL_NAMES.get(args.model_name) in INFERENCE_ONLY:
+        # before any dataset is opened or device touched
+        raise SystemExit(f"audiomodel.py: model {args.model_name!r} is inference only here (predict.py runs its "
+                         "checkpoints); training it is not implemented")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))

@@ -305,7 +305,7 @@ constexpr int conv_g_smem() {
   return a > b ? a : b;
 }
 
-template <typename T, int BM, int BN, int WM, int WN, bool RES = false>
+template <typename T, int BM, int BN, int WM, int WN, bool RES = false, bool LONGK = false>
 __global__ void __launch_bounds__(256, 2)
 k_conv_fwd_g(ConvGeom g, const T* __restrict__ X, const T* __restrict__ Wp, const float* __restrict__ bias,
              T* __restrict__ Y, double* __restrict__ stats, int tiles_m) {
@@ -397,10 +397,22 @@ k_conv_fwd_g(ConvGeom g, const T* __restrict__ X, const T* __restrict__ Wp, cons
       }                                                                                           \
     }
     f4 acc[FM][FN];
+    // LONGK (fp32 dot products of more than CONV_G_LONGK terms, launch_fwd_t):
+    // the sum runs in two levels, acc over FLUSH K-tiles (512 terms) and hi
+    // over those partial sums, so that badwinner2's (44, 3) 128 -> 128 filter
+    // (16 896 terms) is not one accumulation chain whose rounding error grows
+    // with its length (measured 4.4e-6 - 5.1e-6 of the output maximum as one
+    // chain, against 1.3e-6 for a blocked float32 sum)
+    constexpr bool TWO_LEVEL = LONGK && sizeof(T) == 4;
+    constexpr int FLUSH = 16;
+    f4 hi[TWO_LEVEL ? FM : 1][TWO_LEVEL ? FN : 1];
 #pragma unroll
     for (int i = 0; i < FM; ++i)
 #pragma unroll
-      for (int j = 0; j < FN; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < FN; ++j) {
+        acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (TWO_LEVEL) hi[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+      }
 #define CONV_G_COMPUTE(BUF)                                                                       \
     {                                                                                             \
       const unsigned char* Ab = (BUF);                                                            \
@@ -428,6 +440,17 @@ k_conv_fwd_g(ConvGeom g, const T* __restrict__ X, const T* __restrict__ Wp, cons
       // prefetch the next stage (inline-asm DMA: stays in flight under the MFMAs)
       if (kt + 1 < nkt) CONV_G_ISSUE(kt + 1, smem + ((kt + 1) & 1) * STG)
       CONV_G_COMPUTE(cur)
+      if constexpr (TWO_LEVEL) {
+        if (kt % FLUSH == FLUSH - 1 && kt + 1 < nkt) {
+#pragma unroll
+          for (int i = 0; i < FM; ++i)
+#pragma unroll
+            for (int j = 0; j < FN; ++j) {
+              hi[i][j] += acc[i][j];
+              acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+      }
       // next stage landed (vmcnt) and this stage's fragment reads retired
       // (lgkmcnt) before anyone passes the barrier and restages `cur`
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -435,6 +458,14 @@ k_conv_fwd_g(ConvGeom g, const T* __restrict__ X, const T* __restrict__ Wp, cons
     }
 #undef CONV_G_COMPUTE
 #undef CONV_G_ISSUE
+    if constexpr (TWO_LEVEL) {
+      if (nkt > FLUSH) {
+#pragma unroll
+        for (int i = 0; i < FM; ++i)
+#pragma unroll
+          for (int j = 0; j < FN; ++j) acc[i][j] += hi[i][j];
+      }
+    }
     // ---- epilogue: +bias, round, BN statistics of the rounded values, LDS-staged 16-B row stores
     // (g.res: the residual Add (+ReLU) of ops.conv_add is applied in the row
     // stores and the statistics are those of z = (ReLU)(y + res))
@@ -4079,11 +4110,22 @@ static int launch_fwd_rows(const ConvGeom& g, const FwdPick& f, const void* x, c
   return launch_rc("acfe_conv2d_fwd");
 }
 
+// fp32 k_conv_fwd_g: dot products longer than this many terms are summed in two
+// levels (its LONGK variant); shorter ones keep the single chain bit for bit
+constexpr int CONV_G_LONGK = 4096;
+
 // ACFE_FWD_G / ACFE_FWD_GENERIC at BN output channels per tile
 template <typename T, int BN, int WM, int WN>
 static int launch_fwd_t(const ConvGeom& g, const FwdPick& f, const void* x, const void* wp, const float* bias,
                         void* y, double* stats, hipStream_t s) {
   const dim3 grid(f.gx, f.gy);
+  if constexpr (sizeof(T) == 4) {
+    if (f.leaf == ACFE_FWD_G && g.Kdp > CONV_G_LONGK) {
+      hipLaunchKernelGGL((k_conv_fwd_g<T, 128, BN, WM, WN, false, true>), grid, dim3(256), 0, s, g, (const T*)x,
+                         (const T*)wp, bias, (T*)y, stats, f.tiles);
+      return launch_rc("acfe_conv2d_fwd");
+    }
+  }
   if (f.leaf == ACFE_FWD_G)
     hipLaunchKernelGGL((k_conv_fwd_g<T, 128, BN, WM, WN>), grid, dim3(256), 0, s, g, (const T*)x,
                        (const T*)wp, bias, (T*)y, stats, f.tiles);

@@ -9,6 +9,10 @@ as `layers/<layer name>/vars/<i>`, the variables of a layer in
   Conv2D              0 kernel [R, S, Cin, K] (RSCK), 1 bias [K]
   BatchNormalization  0 gamma, 1 beta, 2 moving_mean, 3 moving_variance
   Dense               0 kernel [in, out], 1 bias [out]
+  MagTransform        0 a-power [1]                    (badwinner2.py:33-49)
+A BatchNormalization(scale=False, center=False) (badwinner2's input
+normalisation, badwinner2.py:233) has no gamma / beta: its two variables are
+0 moving_mean, 1 moving_variance.
 The acfe modules keep the reference layer names where the reference sets one
 (conv1_1, res{s}{b}_branch*, bn{s}{b}_branch*, final_bn, prediction); the
 layers the reference leaves unnamed (wr_resnet_bird's stem BN, shortcut and
@@ -18,10 +22,14 @@ the session created before), so they are matched by class and creation
 order: the file's auto-named layers of a class sorted by their numeric
 suffix <-> the module's unnamed layers of that class in construction order.
 Conv kernels are stored KRSC here (w_keras = w.permute(1, 2, 3, 0)).
+badwinner2 names none of its layers: all of them map by class and creation
+order (mag_transform, batch_normalization .. _7, conv2d .. _7), and its first
+convolution's Cin (1 or 3) is taken from the file.
 
 Parity is unpinned: the reference ships no checkpoint and h5py is absent, so
 the reader is exercised on files this module's writer produces in the Keras 3
-layout (tests/test_keras_weights.py).
+layout (tests/test_keras_weights.py; for badwinner2
+tests/test_badwinner2_host.py, equally unpinned).
 """
 from __future__ import annotations
 
@@ -35,10 +43,13 @@ import torch
 
 import h5lite
 
-_AUTO = re.compile(r"^(conv2d|batch_normalization|dense)(?:_(\d+))?$")
+_AUTO = re.compile(r"^(conv2d|batch_normalization|dense|mag_transform)(?:_(\d+))?$")
 
 
 def _kind(mod) -> str | None:
+    kind = getattr(mod, "keras_kind", None)  # a module that states its Keras class (badwinner2)
+    if kind is not None:
+        return kind
     cls = type(mod).__name__
     if cls in ("Conv2D", "StemConv2D"):
         return "conv2d"
@@ -66,6 +77,10 @@ def _vars(kind, mod):
     if kind == "conv2d":
         return [(mod.weight, lambda t: t.permute(1, 2, 3, 0), lambda a: a.permute(3, 0, 1, 2)),
                 (mod.bias, None, None)]
+    if kind == "mag_transform":
+        return [(mod.a, None, None)]
+    if kind == "batch_normalization" and not hasattr(mod, "gamma"):  # scale=False, center=False
+        return [(mod.moving_mean, None, None), (mod.moving_variance, None, None)]
     if kind == "batch_normalization":
         return [(mod.gamma, None, None), (mod.beta, None, None), (mod.moving_mean, None, None),
                 (mod.moving_variance, None, None)]
@@ -132,6 +147,12 @@ def load_keras_weights(model: torch.nn.Module, path, strict=True) -> dict:
                 v = torch.from_numpy(np.ascontiguousarray(a)).to(torch.float32)
                 if to_torch is not None:
                     v = to_torch(v)
+                flex = getattr(mod, "keras_flex_cin", ())
+                if (t is getattr(mod, "weight", None) and v.dim() == 4 and v.shape[:3] == t.shape[:3]
+                        and v.shape[3] != t.shape[3] and v.shape[3] in flex):
+                    # the first convolution keeps the checkpoint's Cin
+                    mod.weight = torch.nn.Parameter(v.to(t.device).contiguous())
+                    continue
                 if tuple(v.shape) != tuple(t.shape):
                     raise ValueError(f"{fname}: shape {tuple(v.shape)} vs model {tuple(t.shape)}")
                 t.copy_(v.to(t.device))

@@ -559,7 +559,7 @@ def detect_tracks(frames, sr=SR, detector="host", dev_out=None):
 class Predictor:
     def __init__(self, checkpoint_dir, device=None, dtype=None):
         from acfe.train import FrontEnd
-        from audiomodel import build_model
+        from audiomodel import MODEL_NAMES, build_model
 
         d = Path(checkpoint_dir)
         self.meta = json.loads((d / "metadata.txt").read_text())
@@ -567,14 +567,25 @@ class Predictor:
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         dt = dtype or (torch.bfloat16 if self.meta.get("dtype", "bf16") == "bf16" else torch.float32)
         n_mels = self.meta.get("n_mels", 160)
-        self.model = build_model(self.meta.get("name", "wr-resnet"), (n_mels, 513, 3), len(self.labels), dt)
-        self.frontend = FrontEnd(n_mels=n_mels, n_fft=self.meta.get("n_fft", 4096), hop=self.meta.get("hop_length", 281),
-                                 fmin=self.meta.get("fmin", 100), fmax=self.meta.get("fmax", 11000),
-                                 break_freq=self.meta.get("break_freq", 1000), pcen=self.meta.get("pcen", True),
-                                 dtype=dt, device=self.device, power=self.meta.get("power", 2))
-        holder = torch.nn.ModuleList([self.frontend, self.model])
+        name = self.meta.get("name", "wr-resnet")
+        bw2 = MODEL_NAMES.get(name) == "badwinner2"
+        sd = None
         if (d / "model.pt").exists():
             sd = torch.load(d / "model.pt", map_location="cpu", weights_only=True)
+        # badwinner2's first convolution keeps the checkpoint's Cin (a Keras file's is read by its loader)
+        cin = sd["1.trunk.0.weight"].shape[-1] if bw2 and sd is not None else 3
+        self.model = build_model(name, (n_mels, 513, cin), len(self.labels), dt,
+                                 multi_label=self.meta.get("multi_label", True), lme=self.meta.get("lme", False))
+        # badwinner2 takes the fp32 mel power itself, whatever the metadata says of
+        # PCEN: its MagTransform is the compression (reference predict.py:874-887)
+        self.frontend = FrontEnd(n_mels=n_mels, n_fft=self.meta.get("n_fft", 4096), hop=self.meta.get("hop_length", 281),
+                                 fmin=self.meta.get("fmin", 100), fmax=self.meta.get("fmax", 11000),
+                                 break_freq=self.meta.get("break_freq", 1000),
+                                 pcen=False if bw2 else self.meta.get("pcen", True),
+                                 dtype=torch.float32 if bw2 else dt, device=self.device,
+                                 power=self.meta.get("power", 2))
+        holder = torch.nn.ModuleList([self.frontend, self.model])
+        if sd is not None:
             holder.load_state_dict(sd)
         else:  # a reference checkpoint dir: {run}.keras / *.weights.h5 (predict.py:746-789)
             from keras_weights import load_keras_weights
@@ -586,6 +597,14 @@ class Predictor:
         holder.to(self.device).eval()
         self._detector = None  # acfe.tracks.SignalDetector of predict_tracks(detector="gpu")
 
+    def _probabilities(self, feats):
+        """The model's outputs for front-end features: its own activation over
+        its logits where it names one (badwinner2: softmax for a single-label
+        checkpoint, else sigmoid), ops.sigmoid for the two WRNs."""
+        from acfe import ops
+
+        return getattr(self.model, "activation", ops.sigmoid)(self.model(feats))
+
     @torch.no_grad()
     def predict_windows(self, recording, stride=1.0, batch_size=1024, pad_mode="constant", pcen_scope="batch"):
         """Sigmoid outputs [n_windows, classes] for 3 s windows every `stride` s
@@ -594,8 +613,6 @@ class Predictor:
         batch_size windows, "window" over every window by itself, so that a
         window's output depends on nothing else; there are no tracks here, so
         "track" is a ValueError."""
-        from acfe import ops
-
         if pcen_scope not in ("batch", "window"):
             raise ValueError(f"pcen scope {pcen_scope!r}: expected 'batch' or 'window' for windows without tracks")
         n = SR * 3
@@ -617,7 +634,7 @@ class Predictor:
             cnt = min(batch_size, n_win - first)
             segs = np.arange(cnt + 1, dtype=np.int32) if pcen_scope == "window" else None
             feats = self.frontend.forward_windows(dev_rec, first, cnt, n=n, hop=hop, pad_mode=pad_mode, segments=segs)
-            out.append(ops.sigmoid(self.model(feats)))
+            out.append(self._probabilities(feats))
         return torch.cat(out).float().cpu().numpy()
 
     @torch.no_grad()
@@ -627,12 +644,10 @@ class Predictor:
         a table of pcen_segments' form over the B windows; PCEN then normalises
         every segment by its own extrema, and the launches are cut at segment
         boundaries (segment_launches).  None: the extrema of each launch."""
-        from acfe import ops
-
         out = []
         for a, b, seg in segment_launches(len(clips), batch_size, segments):
             x = torch.from_numpy(np.ascontiguousarray(clips[a:b], np.float32)).to(self.device)
-            out.append(ops.sigmoid(self.model(self.frontend(x, pad_mode="constant", segments=seg))))
+            out.append(self._probabilities(self.frontend(x, pad_mode="constant", segments=seg)))
         return torch.cat(out).float().cpu().numpy()
 
     @torch.no_grad()
@@ -643,13 +658,12 @@ class Predictor:
         cut and normalised by one kernel per launch of up to batch_size
         windows; segments as in predict_clips."""
         from acfe import frontend as fe
-        from acfe import ops
 
         n = SR * 3
         out = []
         for a, b, seg in segment_launches(len(plan), batch_size, segments):
             x = fe.normalize_windows(rec, plan[a:b], n)
-            out.append(ops.sigmoid(self.model(self.frontend.features(x, pad_mode="constant", segments=seg))))
+            out.append(self._probabilities(self.frontend.features(x, pad_mode="constant", segments=seg)))
         return torch.cat(out).float().cpu().numpy()
 
     def predict_tracks(self, frames, threshold=None, batch_size=1024, rng=None, detector="host", windows="host",
@@ -762,7 +776,8 @@ def main(argv=None):
     ap.add_argument("--pcen-scope", choices=PCEN_SCOPES, default="batch",
                     help="the windows that share PCEN's min / max: every launch of --batch-size windows, each "
                          "track's own windows in runs of 32 as the reference's model.predict per track "
-                         "(--mode tracks only), or each window alone")
+                         "(--mode tracks only), or each window alone; no effect on a model without PCEN "
+                         "(badwinner2, or pcen false in the metadata)")
     a = ap.parse_args(argv)
     if a.mode == "windows" and a.pcen_scope == "track":
         ap.error("--pcen-scope track needs --mode tracks: --mode windows has no tracks")

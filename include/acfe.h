@@ -836,6 +836,38 @@ int64_t acfe_pcen_segments_workspace(int batch, int64_t clip_elems);
 int acfe_pcen_normalize_segments(const float* y_bmt, int batch, int64_t clip_elems, const int32_t* seg_start,
                                  int n_seg, void* out, int out_dtype, float* seg_minmax, void* ws, void* stream);
 
+/* ---- badwinner2 inference (csrc/bw2.hip): the eval-mode layers between its
+ * convolutions (badwinner2.py:212-324). */
+/* MagTransform (badwinner2.py:33-49) followed by the input
+ * BatchNormalization(axis=1, scale=False, center=False) (:233) in eval mode,
+ * over the fp32 mel power x [B][M][T]:
+ *   y[b][m][t] = (x^sigmoid(a[0]) - mean[m]) * (1 / sqrt(var[m] + eps))
+ * in fp32, rounded once to y_dtype (F32 or BF16).  a (one float), mean and var
+ * ([M] moving statistics) are device pointers; the sigmoid is taken on the
+ * device.  The power is exp2(p log2 x) on the hardware transcendentals: x = 0
+ * gives exactly -mean * inv, inv the float rounding of 1 / sqrt(var + eps) formed
+ * in double; x < 0 gives NaN.  x and y must
+ * not overlap; 16-B loads are taken wherever the flat index allows them, for
+ * any T and any 4-B aligned x.  ACFE_E_INVAL: a null pointer, B < 0, M < 1,
+ * M > 4096, T < 1, eps < 0, a misaligned pointer or another dtype. */
+int acfe_mag_rownorm(const float* x, int B, int M, int T, const float* a, const float* mean, const float* var,
+                     float eps, void* y, int y_dtype, void* stream);
+/* LeakyReLU(alpha) -> BatchNormalization in eval mode (badwinner2.py:236-237
+ * ... :296-297) over NHWC [rows][C], fp32 or bf16:
+ *   y = scale[c] * (x > 0 ? x : alpha * x) + shift[c]
+ * in fp32 with one rounding on store; scale = gamma / sqrt(moving_variance +
+ * eps), shift = beta - moving_mean * scale (fp32 [C]).  scale = shift = NULL:
+ * the bare LeakyReLU of :307.  y == x (in place) is allowed.  16-B accesses
+ * when C * sizeof(T) % 16 == 0 and every pointer is 16-B aligned, else a
+ * scalar kernel.  ACFE_E_INVAL: a null x / y, only one of scale / shift,
+ * rows < 0, C < 1, a pointer not aligned to its element, another dtype. */
+int acfe_leaky_bn(const void* x, long long rows, int C, float alpha, const float* scale, const float* shift,
+                  void* y, int dtype, void* stream);
+/* softmax over the rows of fp32 z [B][L] (badwinner2.py:321), the row maximum
+ * subtracted first, one wave per row, any L >= 1.  ACFE_E_INVAL: a null
+ * pointer, B < 0, L < 1. */
+int acfe_softmax(const float* z, int B, int L, float* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
